@@ -17,7 +17,13 @@ solves its own S scenes (weak scaling) and the ranks all-gather the optimal
 controls over RCCL (the north star's exchange step).  The single-scene
 (configs[1] exactly, latency-bound) rate is reported beside it in "single_scene".
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--scenes S] [--cpu-seconds T]
+A plain run sets up, warms up, times the K steps and prints the headline line.  --full adds every other
+leg to the same line: the iLQR (configs[2]), Hybrid A* + tracker (configs[3]) and closed-loop lines with
+their recorded per-kernel rooflines, the configs[4]-whole and single-scene lines and the CPU baselines
+(--no-extras / --no-whole / --no-single / --no-cpu drop single legs of it).  --dump-outputs DIR writes what
+the last timed step returned as DIR/<name>.npy.
+
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--scenes S] [--full [--cpu-seconds T]] [--dump-outputs DIR]
 """
 import argparse
 import ctypes
@@ -69,7 +75,15 @@ def parse():
     ap.add_argument("--no-extras", action="store_true", help="skip the iLQR (configs[2]) and Hybrid A* (configs[3]) lines")
     ap.add_argument("--share-device", action="store_true",
                     help="rehearsal of N>1 on a one-GPU box: every rank on cuda:0, gloo instead of RCCL")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="every leg beside the headline: iLQR, Hybrid A*, tracker, closed loop, configs[4] whole, "
+                         "single scene, CPU baselines (the --no-* options drop single legs of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned as DIR/<name>.npy")
+    a = ap.parse_args()
+    if not a.full:  # a plain run: the headline only
+        a.no_cpu = a.no_single = a.no_whole = a.no_extras = True
+    return a
 
 
 def algorithmic_bytes(S, K, H):
@@ -112,8 +126,31 @@ def gather_f64(vals, dev):
     return [p.tolist() for p in parts]
 
 
-def run(a, S, ctx, dev, world, rank, steps, warmup, rotate, cfg5=True, nstreams=1):
+DUMP_ROLLOUTS = 1024  # rollouts of the TrajectoryCollection --dump-outputs keeps (a seeded sample of the K)
+
+
+def dump_outputs(path, b, K, rank):
+    """--dump-outputs: what one plan call returned (the output set b of run()) as path/<name>.npy, float64.
+    Whole: MPPICtrl, the final rollout, cost, feasible, the counts, every rollout's cost and flag.  The
+    TrajectoryCollection's states and controls (240 MB at S=8): at most DUMP_ROLLOUTS rollouts, the same ones
+    every run (their indices in rollout_index.npy).  Ranks past the first add .rankR to the names."""
+    os.makedirs(path, exist_ok=True)
+    S, H = b["cctrl"].shape[0], b["cctrl"].shape[1]
+    n = max(1, min(K, DUMP_ROLLOUTS, 48_000_000 // (S * ((H + 1) * 7 + H * 2) * 8)))  # under 64 MB in all
+    idx = np.sort(np.random.default_rng(20260415).choice(K, size=n, replace=False))
+    didx = torch.as_tensor(idx, device=b["ctraj"].device)
+    arrays = {"U": b["U"], "traj": b["traj"], "cost": b["cost"], "feasible": b["feas"], "rollout_count": b["rc"],
+              "feasibility_count": b["fc"], "coll_cost": b["ccost"], "coll_feasible": b["cfeas"],
+              "coll_traj_sample": b["ctraj"].index_select(3, didx), "coll_ctrl_sample": b["cctrl"].index_select(2, didx),
+              "rollout_index": didx}
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + (f".rank{rank}" if rank else "") + ".npy"),
+                t.cpu().numpy().astype(np.float64))
+
+
+def run(a, S, ctx, dev, world, rank, steps, warmup, rotate, cfg5=True, nstreams=1, dump=None):
     """Time `steps` plan calls of S scenes; returns (elapsed_s_max, kernel_ms_mean, valid, K, H, fc, fields).
+    dump: a directory for the outputs of the last timed call (dump_outputs), written after the timed region.
     cfg5: the scenes are rank r's block [rS, (r+1)S) of configs[4]'s 64 (own X0 and own obstacle_field.mat
     grid each, configs.cfg5_shard); else S copies of configs[1]'s scene.
     nstreams > 1: consecutive (independent) calls alternate over that many contexts -- one stream each --
@@ -210,6 +247,8 @@ def run(a, S, ctx, dev, world, rank, steps, warmup, rotate, cfg5=True, nstreams=
     kern_ms = ms_sum / max(1, cnt)
     ok = all(bool((b["rc"] == K + 1).all().item()) and bool(torch.isfinite(b["cost"]).all().item())
              for b in sets[: min(len(sets), warmup + steps)])
+    if dump and steps > 0:
+        dump_outputs(dump, sets[(warmup + steps - 1) % len(sets)], K, rank)
     if world > 1:
         rows = gather_f64([elapsed, kern_ms, 0.0 if ok else 1.0], dev)
         elapsed, kern_ms = max(r[0] for r in rows), max(r[1] for r in rows)
@@ -250,7 +289,7 @@ def main():
     torch.cuda.set_stream(stream)  # RCCL all_gather is ordered after the plan kernel
 
     S = a.scenes
-    # The GPU legs of the extras (iLQR, Hybrid A*, tracker, closed loop) run first and the headline after
+    # --full: the GPU legs of the extras (iLQR, Hybrid A*, tracker, closed loop) run first and the headline after
     # them, on a GPU that has been busy for seconds as in continuous serving: after an idle box, W = 5
     # warmup steps (1.5 ms of work) leave the clocks ramping through a short timed region (r04d: 20 timed
     # steps give a 0.298 ms plan kernel after 5 warmup steps, 0.280 ms after 2,000).  The timed region
@@ -262,7 +301,7 @@ def main():
         extras["hybrid_astar"] = bench_hastar(ctx, world, rank, cpu=cpu_jobs)
         extras["closed_loop"] = bench_closed_loop(ctx, world, rank, cpu=cpu_jobs)
     elapsed, kern_ms, ok, K, H, fc, fields = run(a, S, ctx, dev, world, rank, a.steps, a.warmup, a.rotate,
-                                                 nstreams=max(1, a.streams))
+                                                 nstreams=max(1, a.streams), dump=a.dump_outputs)
     value = world * S * K * H * a.steps / elapsed
     nbytes = algorithmic_bytes(S, K, H)
     # the device time per launch: with one stream the launch's own HIP-event span; with several the launches

@@ -70,3 +70,50 @@ def test_leg_ranking_and_bench_roofline(tmp_path):
     assert out["frac"] == pipe["valu_frac"] and out["share_of_leg"] == pipe["share"]
     assert [k["name"] for k in out["kernels"]] == names
     assert bench.leg_roofline(rl, "ha_plan") is None
+
+
+def test_bench_plain_run_is_headline_only(monkeypatch):
+    """Without --full every leg beside the headline is off; --full turns them on and the --no-* options
+    still drop single legs of it."""
+    sys.path.insert(0, ROOT)
+    bench = _load("bench.py", "bench_mod")
+    legs = ("no_cpu", "no_single", "no_whole", "no_extras")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert all(getattr(a, k) for k in legs) and a.steps == 7 and a.warmup == 2 and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-single"])
+    a = bench.parse()
+    assert [getattr(a, k) for k in legs] == [False, True, False, False]
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs: float64 .npy files, the small outputs whole, the TrajectoryCollection as the same
+    seeded sample of rollouts every time (indices beside it), under 64 MB at the headline's shape."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    bench = _load("bench.py", "bench_mod")
+    S, H, K = 2, 5, 3000
+    g = torch.Generator().manual_seed(1)
+    b = dict(U=torch.rand((S, H, 2), dtype=torch.float64, generator=g),
+             traj=torch.rand((S, H + 1, 7), dtype=torch.float64, generator=g),
+             cost=torch.rand(S, dtype=torch.float64, generator=g), feas=torch.ones(S, dtype=torch.int32),
+             rc=torch.full((S,), K + 1, dtype=torch.int32), fc=torch.full((S,), 9, dtype=torch.int32),
+             ctraj=torch.rand((S, H + 1, 7, K), dtype=torch.float64, generator=g),
+             cctrl=torch.rand((S, H, K, 2), dtype=torch.float64, generator=g),
+             ccost=torch.rand((S, K), dtype=torch.float64, generator=g), cfeas=torch.ones((S, K), dtype=torch.uint8))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), b, K, 0)
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert all(np.array_equal(v, np.load(tmp_path / "b" / (k + ".npy"))) for k, v in got.items())
+    idx = got["rollout_index"].astype(int)
+    assert len(idx) == bench.DUMP_ROLLOUTS and len(set(idx)) == len(idx) and idx.min() >= 0 and idx.max() < K
+    assert np.array_equal(got["U"], b["U"].numpy()) and np.array_equal(got["coll_cost"], b["ccost"].numpy())
+    assert np.array_equal(got["rollout_count"], np.full(S, K + 1.0))
+    assert np.array_equal(got["coll_traj_sample"], b["ctraj"].numpy()[:, :, :, idx])
+    assert np.array_equal(got["coll_ctrl_sample"], b["cctrl"].numpy()[:, :, idx])
+    # the headline's shape (S=8, H=50, K=8192): whole outputs + the sample stay under the 64 MB limit
+    n = min(8192, bench.DUMP_ROLLOUTS)
+    assert 8 * (8 * (51 * 7 + 50 * 2) * n + 8192 * 2 + 50 * 2 + 51 * 7 + 4) + 8 * n < 64e6

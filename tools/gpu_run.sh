@@ -4,7 +4,7 @@
 # usage: bash tools/gpu_run.sh TAG STEP [STEP ...]
 #   tests[:PYTEST-ARGS]  the GPU suite (pytest -m gpu), e.g. tests or "tests:tests/test_gpu_ilqr.py -k solve"
 #   smoke                __graft_entry__.smoke()
-#   bench[:ARGS]         python bench.py ARGS (default: the driver's --steps 20 --warmup 5)
+#   bench[:ARGS]         python bench.py ARGS (default: every leg at the short arguments, --full --steps 20 --warmup 5)
 #   prof                 rocprofv3 kernel-trace stats of a short bench run
 #   pass                 tools/gpu_pass4.sh's PMC / roofline / bench chain (its own output dir)
 #   cmd:COMMAND          any other command (its output to TAG/cmdN.log)
@@ -28,11 +28,11 @@ for step in "$@"; do
       timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
       rc=$?; tail -3 $O/smoke.log ;;
     bench)
-      timeout -k 10 600 python bench.py ${arg:---steps 20 --warmup 5} > $O/bench_$n.log 2>&1
+      timeout -k 10 600 python bench.py ${arg:---full --steps 20 --warmup 5} > $O/bench_$n.log 2>&1
       rc=$?; tail -c 2500 $O/bench_$n.log ;;
     prof)
       timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- \
-        python3 bench.py --steps 30 --warmup 3 --no-cpu > $O/prof.log 2>&1
+        python3 bench.py --full --steps 30 --warmup 3 --no-cpu > $O/prof.log 2>&1
       rc=$?; find $O -name 'run_kernel_trace.csv' | xargs -r gzip -f ;;
     pass)
       bash tools/gpu_pass4.sh ${TAG}_pass_notest

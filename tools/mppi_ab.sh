@@ -6,7 +6,7 @@ set -o pipefail
 TAG=$1; shift
 D=gpurun_out/$TAG; mkdir -p $D
 export TMPDIR=/tmp
-B="python3 bench.py --steps 20 --warmup 3 --no-cpu --no-extras"
+B="python3 bench.py --full --steps 20 --warmup 3 --no-cpu --no-extras"
 for v in "$@"; do
   n=${v:-default}
   export MPGPU_LIB=$PWD/motionplanning_amd/lib/libmpgpu$v.so
