@@ -340,7 +340,9 @@ int mp_ha_set_primitives(mp_ctx* ctx, const mp_ha_params* p, const double* state
  * out: nb_states[B][n_prim][3] regulated neighbor states,
  *      idx[B][n_prim]  Encode (0 = out of bounds),
  *      free_[B][n_prim] 1 if in bounds and dg_cost finite (collision free),
- *      h[B][n_prim]     rs_heuristic (valid where free_ == 1). */
+ *      h[B][n_prim]     rs_heuristic (valid where free_ == 1).  It stays the Reeds-Shepp heuristic
+ *                       alone: astar_heuristic (use_astar) is applied by mp_ha_plan_astar where it
+ *                       forms temp_h, from mp_ha_astar_table's table. */
 int mp_ha_expand(mp_ctx* ctx, const mp_ha_params* p, int32_t B, const double* node,
                  const double* goal, const double* walls, double* nb_states, int64_t* idx,
                  uint8_t* free_, double* h);
@@ -381,6 +383,26 @@ int mp_ha_plan(mp_ctx* ctx, const mp_ha_params* p, int32_t B, const double* star
                int32_t* n_nodes, int64_t* pop_seq, int32_t* n_states, double* states_out,
                int32_t* rs_len, double* rs_path);
 
+/* astar_heuristic (hybrid_astar_utils.jl:375-387) for B Hybrid A* scenes: the final_cost of planAstar!
+ * on the 11 x 11 grid over stbound's x/y box with the scene's walls as block obstacles, from every cell
+ * to the cell of goal[B][3]'s (x, y).  planAstar! depends on the state only through its start cell
+ * (Astar/src/setup.jl:17), so the heuristic of a state (x, y) of scene b is
+ *   table[b][(iy - 1) * 11 + (ix - 1)],  ix = Int(floor((x - xmin) / x_factor + 1)),
+ *                                         iy = Int(floor((y - ymin) / y_factor + 1))   (1-based cells),
+ * x_factor = (xmax - xmin) / 10.  0.0 where the goal cannot be reached (final_cost's initial value) and
+ * in the goal's own cell (see mp_astar_plan).  walls[B][n_walls][5]; n_walls = 0: all cells free. */
+int mp_ha_astar_table(mp_ctx* ctx, const mp_ha_params* p, int32_t B, const double* goal, const double* walls,
+                      double* table);
+
+/* mp_ha_plan with HybridAstarSettings.use_astar (types.jl:37).  use_astar = 0: mp_ha_plan exactly.
+ * use_astar = 1: the table of mp_ha_astar_table is built on the device ahead of the search and every
+ * child's temp_h is max(rs_heuristic, astar_heuristic) (hybrid_astar_utils.jl:419, Julia's max: NaN
+ * propagates).  Same outputs as mp_ha_plan. */
+int mp_ha_plan_astar(mp_ctx* ctx, const mp_ha_params* p, int32_t B, const double* start,
+                     const double* goal, const double* walls, int32_t use_astar, int32_t* found,
+                     int32_t* pops, int32_t* n_nodes, int64_t* pop_seq, int32_t* n_states,
+                     double* states_out, int32_t* rs_len, double* rs_path);
+
 /* retrievePath + cubic_fit (PathPlanning/HybridAstar/src/hybrid_astar_utils.jl:100-177) for B planned
  * scenarios, one block each: actualpath = [starting_states, cubic_fit(states[:,i], states[:,i+1]) (100
  * points each, i over the hybrid_astar_states reversed to start -> goal order), RSpath_final], its
@@ -397,6 +419,34 @@ int mp_ha_retrieve_path(mp_ctx* ctx, int32_t B, const double* start, const int32
                         int32_t state_stride, const int32_t* rs_len, const double* rs_path, int64_t* path_offset,
                         double* actualpath, double* path_length, int32_t* n_points, double* tol_length,
                         double* samples);
+
+/* ------------------------------------------------------------ grid A* */
+/* planAstar! (PathPlanning/Astar/src/astar_utils.jl:83-141 with FindNewNode :190-235) for B independent
+ * searches on nx x ny grids (defineAstar, Astar/src/setup.jl:3-24), one wavefront per search with its
+ * node table and open list in LDS; the free-cell mask (checkObsSafety) of each search's scene is
+ * computed once, ahead of it.  nx, ny >= 2 and nx*ny <= 51*51 (MP_ERR_INVALID beyond).
+ * in : bound[B][4] (actualbound: xmin, xmax, ymin, ymax), start_real[B][2], goal_real[B][2],
+ *      obs_kind 3 (circles [x, y, r]) or 5 (blocks [x, y, psi, l/2, w/2]),
+ *      obstacles[B][n_obs][obs_kind].
+ * out: final_cost[B], found[B], pops[B] (loop_count), n_nodes[B] (length(nodes_collection)).
+ * optional (NULL: not returned):
+ *      pop_seq[B][2*(nx*ny+1)]  Encode index, (y-1)*nx + x, of every popped cell, -1 padded
+ *                               (0: a start cell off the grid);
+ *      astarpath[B][nx*ny+1] with path_n[B] (both or neither): the path's Encode indices, start -> goal;
+ *      path_length[B]           astar.r.path_length.
+ * Cells, costs and the pop order are the reference's (a stable sort of the open list by f every
+ * iteration, nodes updated in place, closed nodes re-opened).  Two inputs on which the reference itself
+ * fails are defined here:
+ *   - start cell == goal cell: the reference sets final_cost = 0 and then throws KeyError(nothing)
+ *     (astar_utils.jl:110); here cost 0, found, a one-cell path of length 0;
+ *   - an empty obstacle list (n_obs = 0): the reference indexes obstacle_list[1]; here every cell is free.
+ * An unreachable goal (or one off the grid) leaves final_cost = 0.0, found = 0.  The loop is bounded by
+ * 2*(nx*ny+1) pops; a search that reaches the bound makes the call return MP_ERR_NUMERIC (outputs
+ * written). */
+int mp_astar_plan(mp_ctx* ctx, int32_t B, int32_t nx, int32_t ny, const double* bound, const double* start_real,
+                  const double* goal_real, int32_t obs_kind, int32_t n_obs, const double* obstacles,
+                  double* final_cost, int32_t* found, int32_t* pops, int32_t* n_nodes, int32_t* pop_seq,
+                  int32_t* astarpath, int32_t* path_n, double* path_length);
 
 /* ------------------------------------------------------- path tracker */
 /* Settings of the Hybrid A* path tracker (PathPlanning/HybridAstar/main_Tracker.jl:42-72). */

@@ -29,7 +29,7 @@ module MPGPU
 using Interpolations: interpolate, Gridded, Constant, Previous, linear_interpolation   # as the reference drivers
 
 export MPPIPlan, MPPIClosedLoop, planHybridAstar!, mppi_plan_batch, mppi_plan_sharded, comm_init, mppi_closed_loop_batch,
-       rollout_batch, ha_expand, ha_rs_connect,
+       rollout_batch, ha_expand, ha_rs_connect, ha_astar_table, astar_plan_batch,
        ha_allpath, ha_neighbor_origin, retrieve_batch!, track_batch!, ilqr_rollout, ilqr_backward!, ilqr_forward!,
        ilqr_solve!, vehicle_euler!, ctx_join
 
@@ -415,9 +415,13 @@ Drop-in for hybrid_astar_utils.jl:235-296 (one scenario; `plan_batch!` for many)
 `ha.r.RSpath_final` (3×len), `ha.p.loop_count` and `ha.r.planning_time`, then calls the
 reference's own `retrievePath(ha)` when a path was found.
 """
-planHybridAstar!(ha; retrieve = nothing) = (plan_batch!([ha]; retrieve = retrieve); nothing)
+planHybridAstar!(ha; retrieve = nothing, use_astar = ha.s.use_astar) =
+    (plan_batch!([ha]; retrieve = retrieve, use_astar = use_astar); nothing)
 
-function plan_batch!(has::AbstractVector; retrieve = nothing, max_pops = 5000)
+# `use_astar`: HybridAstarSettings.use_astar (types.jl:37) -- temp_h = max(rs_heuristic, astar_heuristic), the
+# grid-A* table built on the device ahead of the search (mp_ha_plan_astar); every scene of a batch shares it
+function plan_batch!(has::AbstractVector; retrieve = nothing, max_pops = 5000, use_astar = has[1].s.use_astar)
+    all(h -> h.s.use_astar == has[1].s.use_astar, has) || error("plan_batch!: every scene needs the same use_astar")
     t1 = time()
     h0 = has[1]
     p = ha_params(h0; max_pops = max_pops)
@@ -429,10 +433,17 @@ function plan_batch!(has::AbstractVector; retrieve = nothing, max_pops = 5000)
     seq = fill(Int64(-1), max_pops, B); ns = zeros(Int32, B); states = zeros(3, max_pops, B)
     rl = zeros(Int32, B); rs = zeros(3, 501, B)
     c = ctx()
-    st = GC.@preserve start goal walls found pops nn seq ns states rl rs ccall((:mp_ha_plan, libmpgpu), Cint,
-        (Ptr{Cvoid}, Ref{HaParams}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32},
-         Ptr{Int32}, Ptr{Int64}, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}),
-        c, p, B, start, goal, walls, found, pops, nn, seq, ns, states, rl, rs)
+    st = if use_astar
+        GC.@preserve start goal walls found pops nn seq ns states rl rs ccall((:mp_ha_plan_astar, libmpgpu), Cint,
+            (Ptr{Cvoid}, Ref{HaParams}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Int32}, Ptr{Int32},
+             Ptr{Int32}, Ptr{Int64}, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}),
+            c, p, B, start, goal, walls, 1, found, pops, nn, seq, ns, states, rl, rs)
+    else
+        GC.@preserve start goal walls found pops nn seq ns states rl rs ccall((:mp_ha_plan, libmpgpu), Cint,
+            (Ptr{Cvoid}, Ref{HaParams}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32},
+             Ptr{Int32}, Ptr{Int64}, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}),
+            c, p, B, start, goal, walls, found, pops, nn, seq, ns, states, rl, rs)
+    end
     check(st, c)
     dt = time() - t1
     for (b, h) in enumerate(has)
@@ -447,8 +458,48 @@ function plan_batch!(has::AbstractVector; retrieve = nothing, max_pops = 5000)
     return (; found, pops, n_nodes = nn, pop_sequence = seq)
 end
 
-"""Batched FindNewNode device part for B popped nodes (3, B): neighbour states (3, n, B),
-Encode indices (n, B) (0 = out of bounds), collision-free flags (n, B), rs heuristics (n, B)."""
+"""
+    ha_astar_table(p, goal, walls)
+
+astar_heuristic (hybrid_astar_utils.jl:375-387) of B scenes for a state in every cell of the 11 × 11 grid
+(mp_ha_astar_table): goal (3, B), walls (5, n_walls, B) -> (11, 11, B), `table[ix, iy, b]` for the 1-based cell
+`(ix, iy)` of Astar/src/setup.jl:17.
+"""
+function ha_astar_table(p::HaParams, goal::Matrix{Float64}, walls::Array{Float64,3})
+    B = size(goal, 2)
+    table = zeros(11, 11, B)
+    c = ctx()
+    check(GC.@preserve goal walls table ccall((:mp_ha_astar_table, libmpgpu), Cint,
+        (Ptr{Cvoid}, Ref{HaParams}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), c, p, B, goal, walls, table), c)
+    return table
+end
+
+"""
+    astar_plan_batch(mapbound, bound, start_real, goal_real, obstacles)
+
+planAstar! (PathPlanning/Astar/src/astar_utils.jl:83-141) for B searches (mp_astar_plan): mapbound = (nx, ny),
+bound (4, B) = actualbound, start_real / goal_real (2, B), obstacles (3 or 5, n_obs, B).  Returns final_cost,
+found, loop_count, n_nodes, the pop sequence (Encode indices, -1 padded), astarpath as Encode indices with its
+length per search, and path_length.
+"""
+function astar_plan_batch(mapbound, bound::Matrix{Float64}, start_real::Matrix{Float64}, goal_real::Matrix{Float64},
+                          obstacles::Array{Float64,3})
+    nx, ny = Int(mapbound[1]), Int(mapbound[2])
+    B = size(bound, 2); M = nx * ny + 1
+    kind = size(obstacles, 1); n_obs = size(obstacles, 2)
+    cost = zeros(B); plen = zeros(B)
+    found = zeros(Int32, B); pops = zeros(Int32, B); nn = zeros(Int32, B); pn = zeros(Int32, B)
+    seq = zeros(Int32, 2M, B); path = zeros(Int32, M, B)
+    c = ctx()
+    check(GC.@preserve bound start_real goal_real obstacles cost plen found pops nn pn seq path ccall((:mp_astar_plan, libmpgpu), Cint,
+        (Ptr{Cvoid}, Int32, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Ptr{Float64},
+         Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}),
+        c, B, nx, ny, bound, start_real, goal_real, kind, n_obs, obstacles, cost, found, pops, nn, seq, path, pn,
+        plen), c)
+    return (; final_cost = cost, found, loop_count = pops, n_nodes = nn, pop_sequence = seq, astarpath = path,
+            path_n = pn, path_length = plen)
+end
+
 """
     retrieve_batch!(has)
 

@@ -179,6 +179,9 @@ SIGNATURES = {
     "mp_ha_allpath": (ctypes.c_int, [_V, _I, _V, _V, _V, _V]),
     "mp_ha_sat_cull_active": (ctypes.c_int, [_V, ctypes.POINTER(HAParams), _I, _V, _V, _V, _V]),
     "mp_ha_plan": (ctypes.c_int, [_V, ctypes.POINTER(HAParams), _I] + [_V] * 11),
+    "mp_ha_plan_astar": (ctypes.c_int, [_V, ctypes.POINTER(HAParams), _I, _V, _V, _V, _I] + [_V] * 8),
+    "mp_ha_astar_table": (ctypes.c_int, [_V, ctypes.POINTER(HAParams), _I, _V, _V, _V]),
+    "mp_astar_plan": (ctypes.c_int, [_V, _I, _I, _I, _V, _V, _V, _I, _I] + [_V] * 9),
     "mp_ha_retrieve_path": (ctypes.c_int, [_V, _I, _V, _V, _V, _I] + [_V] * 8),
     "mp_ha_track": (ctypes.c_int, [_V, ctypes.POINTER(TrackParams), _I, _V, _V, _V, _I] + [_V] * 6 + [_I]),
     "mp_math_eval": (ctypes.c_int, [_V, _I, ctypes.c_int64, _V, _V, _V]),

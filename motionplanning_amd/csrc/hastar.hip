@@ -15,6 +15,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <cmath>
 #include <vector>
 
@@ -63,6 +64,14 @@ struct HaDev {
   int n_walls, n_prim, n_col;
   int cull;  // the SAT culls' rounding margins are proven for this call's coordinates (ha_cull_ok); else full SAT
 };
+
+// temp_h = max(rs_heuristic, astar_heuristic) (:419), Julia's max: a NaN operand propagates
+__device__ __forceinline__ double ha_temp_h(double hk, double ah) {
+  double th = __builtin_fmax(hk, ah);
+  if (hk != hk) th = hk;
+  if (ah != ah) th = ah;
+  return th;
+}
 
 // ------------------------------------------------------------ Reeds–Shepp
 __device__ __forceinline__ void polar(double a, double b, double* r, double* th) {
@@ -1717,6 +1726,25 @@ struct HaSearch {
   int* rsrs;             // [2][B] 2·it + 2 once RS_connected(r_it) has run, by it & 1
   int* nhit;             // [2][B] (diagnostics) pops that were the runner-up, runner-ups published
 };
+// astar_heuristic (hybrid_astar_utils.jl:375-387) of scene b's neighbour state (x, y): planAstar! depends on
+// the state only through its start cell, Int(floor((x - xmin)/x_factor + 1)) (Astar/src/setup.jl:17), so it
+// is one lookup in the scene's table (astar.hip).  mp_ha_plan_astar leaves the table's address and the
+// 11 x 11 grid's x_factor / y_factor in the 256-byte slot of Q.err, at byte 8 (AS_HDR): no kernel argument
+// changes, and the use_astar = false instances (AST = false: astar_heuristic returns 0) are the code they
+// were -- a run-time null check in the shared bookkeeping measured 0.3 ms per 256-plan, spills moving around.
+// A neighbour that reaches here is inside stbound (Encode != 0), its cell inside the grid; the clamp only
+// keeps a NaN state's read inside the table.
+constexpr int AS_HDR = 8;
+template <bool AST>
+__device__ __forceinline__ double astar_h(const HaDev& P, const HaSearch& Q, int b, double x, double y) {
+  if (!AST) return 0.0;
+  const double* hd = reinterpret_cast<const double*>(reinterpret_cast<const char*>(Q.err) + AS_HDR);
+  const double* tab = reinterpret_cast<const double*>(__double_as_longlong(hd[0]));
+  int cx = (int)__builtin_floor((x - P.sb[0]) / hd[1] + 1), cy = (int)__builtin_floor((y - P.sb[2]) / hd[2] + 1);
+  cx = cx < 1 ? 1 : cx > 11 ? 11 : cx;
+  cy = cy < 1 ? 1 : cy > 11 ? 11 : cy;
+  return tab[(size_t)b * 121 + (cy - 1) * 11 + (cx - 1)];
+}
 // prescan record: [0] iteration tag, [1] kc = min(K, n_open), then K entries of 13 words: f (bits), seq, position,
 // node id, g (bits), Encode index, state (3, bits), rw, (t, u, v) (3, bits)
 constexpr int PRE_K = 4, PRE_E = 13, PRE_W = 2 + PRE_E * PRE_K;
@@ -2094,8 +2122,7 @@ __device__ void ha_book(const HaDev& P, const HaSearch& Q, const IterArgs& A, in
     int nrw = hwk;  // the node's stored rs_heuristic winner (its open entry carries it)
     double nt0 = tuvk[0], nt1 = tuvk[1], nt2 = tuvk[2];
     if (first) {
-      th = __builtin_fmax(hk, 0.0);
-      if (hk != hk) th = hk;
+      th = ha_temp_h(hk, 0.0);  // (ha_book_kernel serves no plan with use_astar)
       tf = tg + th;
       if (hit >= 0) {
         id = hit;
@@ -2229,7 +2256,7 @@ struct BookRec {
 // FindNewNode + popfirst! for scene b on an NT-thread block (ha_book without its termination branch):
 // the neighbour records are read agent-coherently; the node count, the pop count and pop_seq go to the
 // scene's record (Q.rec) for the finisher instead of the scene's counters.
-template <int NT, bool RSH = false>
+template <int NT, bool RSH = false, bool AST = false>
 __device__ __forceinline__ BookRec ha_book_spec(const HaDev& P, const HaSearch& Q, const IterArgs& A, int B, int it,
                                                 int b, unsigned long long* stp = nullptr) {
 #define BSTAMP(i) if (stp) __hip_atomic_store(stp + (i), __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
@@ -2387,8 +2414,7 @@ __device__ __forceinline__ BookRec ha_book_spec(const HaDev& P, const HaSearch& 
     int nrw = hwk;  // the node's stored rs_heuristic winner (its open entry carries it)
     double nt0 = tuvk[0], nt1 = tuvk[1], nt2 = tuvk[2];
     if (first) {
-      th = __builtin_fmax(hk, 0.0);
-      if (hk != hk) th = hk;
+      th = ha_temp_h(hk, astar_h<AST>(P, Q, b, nb0, nb1));
       tf = tg + th;
       if (hit >= 0) {
         id = hit;
@@ -2888,7 +2914,7 @@ __device__ __forceinline__ IterArgs e_par(const IterArgs& A, int B, int np, int 
 // (10 payload words + valid), and the pop's go word carries skip = hit (the popped node IS the previous
 // runner-up, identical id, state and stored commands: its expansion and RS_connected were made speculatively);
 // *hit_out returns it.
-template <int NT, bool RSH = true, class Wait = NoMid, bool SPEC = false>
+template <int NT, bool RSH = true, class Wait = NoMid, bool SPEC = false, bool AST = false>
 __device__ __forceinline__ BookRec ha_book_pipe(const HaDev& P, const HaSearch& Q, const IterArgs& E, int B, int it,
                                                 int b, unsigned long long* stp = nullptr, const Wait& pre_wait = Wait(),
                                                 long long* sr = nullptr, int* hit_out = nullptr) {
@@ -3032,8 +3058,7 @@ __device__ __forceinline__ BookRec ha_book_pipe(const HaDev& P, const HaSearch& 
     double fo = 0.0;
     long long so_ = 0;
     if (first) {
-      th = __builtin_fmax(hk, 0.0);
-      if (hk != hk) th = hk;
+      th = ha_temp_h(hk, astar_h<AST>(P, Q, b, nb0, nb1));
       tf = tg + th;
       if (hit >= 0) {
         id = hit;
@@ -3447,7 +3472,7 @@ __device__ __forceinline__ BookRec ha_book_pipe(const HaDev& P, const HaSearch& 
 #define HA_WPE_TAIL 1
 #endif
 constexpr int HA_STAMP_EVERY = 25, HA_STAMP_N = 17;  // [6..11]: bookkeeping phases; [12..16]: block body phases
-template <int HWt, int NBGt, bool RSH = false>
+template <int HWt, int NBGt, bool RSH = false, bool AST = false>
 // (the 6-wave middle shape at 3 waves per SIMD -- 139 VGPRs, no spills, still two blocks per CU -- measured 1.4 ms
 // slower per 256-plan than at 4 with 128 VGPRs and spills, r05zp; kept at 4)
 #ifndef HA_WPE_MID
@@ -3501,7 +3526,7 @@ __global__ __launch_bounds__(64 * HWt) __attribute__((amdgpu_waves_per_eu(HWt ==
   // block is running and publishes without waiting on anything).
   long long* rc = Q.rec + (size_t)RC_N * s;
   if (r == 1) {
-    const BookRec br = ha_book_spec<64 * HWt, RSH>(P, Q, A, B, it, s, stp);
+    const BookRec br = ha_book_spec<64 * HWt, RSH, AST>(P, Q, A, B, it, s, stp);
     if (!HA_FIN_SHORTCUT) {  // (A/B) always publish the record first
       if (threadIdx.x == 0) {
 #pragma unroll
@@ -3552,7 +3577,7 @@ __global__ __launch_bounds__(64 * HWt) __attribute__((amdgpu_waves_per_eu(HWt ==
 // ha_pipe_kernel: the pipelined tail's launch (see above).  Items per slot: 0 RS_connected(n_it), 1 the
 // bookkeeping, 2 .. 1 + n_groups the expansion of n_{it+1}.  boot = 1: only the expansion, of n_it itself
 // (node buffer (it - 1) & 1) into E[it & 1], for the first pipelined launch.
-template <int HWt, int NBGt, bool RSH = true>
+template <int HWt, int NBGt, bool RSH = true, bool AST = false>
 __global__ __launch_bounds__(64 * HWt) __attribute__((amdgpu_waves_per_eu(HWt == 4 ? HA_WPE_FULL : HA_WPE_TAIL))) void ha_pipe_kernel(
     HaDev P, HaSearch Q, IterArgs A, int B, int it, int boot) {
   __shared__ int role, sh_go;
@@ -3607,7 +3632,7 @@ __global__ __launch_bounds__(64 * HWt) __attribute__((amdgpu_waves_per_eu(HWt ==
   // the final ticket: RS_connected (item 0) and the bookkeeping (item 1), as in ha_step_kernel
   long long* rc = Q.rec + (size_t)RC_N * s;
   if (item == 1) {
-    const BookRec br = ha_book_pipe<64 * HWt, RSH>(P, Q, e_par(A, B, np, it & 1), B, it, s, stp);
+    const BookRec br = ha_book_pipe<64 * HWt, RSH, NoMid, false, AST>(P, Q, e_par(A, B, np, it & 1), B, it, s, stp);
     if (threadIdx.x == 0) {
       if (stp) __hip_atomic_store(stp + 3, __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (__hip_atomic_fetch_add(Q.tk + B + s, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 1) {
@@ -3661,7 +3686,7 @@ __global__ __launch_bounds__(64 * HWt) __attribute__((amdgpu_waves_per_eu(HWt ==
 #endif
 // blocks per scene of the persistent launch: two RS_connected blocks, the bookkeeping, ng expansion groups
 #define HA_PERSIST_PER(ng) (3 + (ng))
-template <int HWt, int NBGt, bool SPEC = HA_SPEC>
+template <int HWt, int NBGt, bool SPEC = HA_SPEC, bool AST = false>
 __global__ __launch_bounds__(64 * HWt) __attribute__((amdgpu_waves_per_eu(HWt == HW_TAIL ? HA_WPE_TAIL : 3))) void ha_persist_kernel(
     HaDev P, HaSearch Q, IterArgs A, int B, int it0, double* rs_path2, unsigned char* rs_ok2, int* rs_len2) {
   __shared__ int sh_f;
@@ -3806,9 +3831,9 @@ __global__ __launch_bounds__(64 * HWt) __attribute__((amdgpu_waves_per_eu(HWt ==
 #define HA_PREWAIT 1
 #endif
     if (!HA_PREWAIT) wait_exp();  // (A/B build -DHA_PREWAIT=0: the wait before the bookkeeping's first load)
-    const BookRec br = HA_PREWAIT ? ha_book_pipe<NTB, true, decltype(wait_exp), SPEC>(P, Q, Ei, B, it, s, stp,
+    const BookRec br = HA_PREWAIT ? ha_book_pipe<NTB, true, decltype(wait_exp), SPEC, AST>(P, Q, Ei, B, it, s, stp,
                                                                                  wait_exp, sh_run, &hit_next)
-                                  : ha_book_pipe<NTB, true, NoMid, SPEC>(P, Q, Ei, B, it, s, stp, NoMid(), sh_run,
+                                  : ha_book_pipe<NTB, true, NoMid, SPEC, AST>(P, Q, Ei, B, it, s, stp, NoMid(), sh_run,
                                                                    &hit_next);
     put(stp, 3, now());
     IterArgs F = A;
@@ -4217,6 +4242,13 @@ int mp_ha_retrieve_path(mp_ctx* ctx, int32_t B, const double* start, const int32
 int mp_ha_plan(mp_ctx* ctx, const mp_ha_params* p, int32_t B, const double* start, const double* goal,
                const double* walls, int32_t* found, int32_t* pops, int32_t* n_nodes, int64_t* pop_seq,
                int32_t* n_states, double* states_out, int32_t* rs_len, double* rs_path) {
+  return mp_ha_plan_astar(ctx, p, B, start, goal, walls, 0, found, pops, n_nodes, pop_seq, n_states, states_out,
+                          rs_len, rs_path);
+}
+
+int mp_ha_plan_astar(mp_ctx* ctx, const mp_ha_params* p, int32_t B, const double* start, const double* goal,
+                     const double* walls, int32_t use_astar, int32_t* found, int32_t* pops, int32_t* n_nodes,
+                     int64_t* pop_seq, int32_t* n_states, double* states_out, int32_t* rs_len, double* rs_path) {
   if (!ctx) return MP_ERR_INVALID;
   HaDev D;
   int st = make_ha(ctx, p, &D);
@@ -4285,7 +4317,7 @@ int mp_ha_plan(mp_ctx* ctx, const mp_ha_params* p, int32_t B, const double* star
   Q.ngr = (unsigned long long*)take(nB * HA_NGR_SLOTS * HA_NGR * 8);
   Q.ex = (int*)take(nB * 4);
   Q.rsr = (int*)take(nB * 8);
-  Q.err = (int*)take(4);
+  Q.err = (int*)take(AS_HDR + 3 * sizeof(double));  // the flag, and (mp_ha_plan_astar) the table header behind it
   Q.node_g = (double*)take(nB * 16);
   Q.node_nn = (int*)take(nB * 8);
   Q.ngr2 = (unsigned long long*)take(nB * HA_NGR_SLOTS * HA_NGR * 8);
@@ -4296,6 +4328,18 @@ int mp_ha_plan(mp_ctx* ctx, const mp_ha_params* p, int32_t B, const double* star
   A.goal = mp_upload(ctx, WS_HA0, goal, 3 * nB, &st);
   A.walls = p->n_walls ? mp_upload(ctx, WS_HA1, walls, 5 * (size_t)p->n_walls * B, &st) : nullptr;
   const double* dstart = mp_upload(ctx, WS_IO0, start, 3 * nB, &st);
+  if (use_astar) {  // astar_heuristic's table, built on the device ahead of the search (same stream)
+    if (st) return st;
+    const double* tab = nullptr;
+    if ((st = mp_as_table_dev(ctx, p, B, goal, A.walls, &tab))) return st;
+    double* hd = ctx->as_hdr_host;  // (kept by the context: the copy is asynchronous)
+    const long long bits = (long long)reinterpret_cast<uintptr_t>(tab);
+    memcpy(&hd[0], &bits, sizeof bits);
+    hd[1] = (p->stbound[1] - p->stbound[0]) / (11.0 - 1);  // x_factor, y_factor of mapbound [11, 11]
+    hd[2] = (p->stbound[3] - p->stbound[2]) / (11.0 - 1);
+    MP_HIP(ctx, hipMemcpyAsync(reinterpret_cast<char*>(Q.err) + AS_HDR, hd, 3 * sizeof(double), hipMemcpyHostToDevice,
+                               ctx->stream));
+  }
   // the expansion records: 2 parities (E[it & 1]) + (HA_SPEC) 4 runner-up slots
   constexpr size_t NPAR = HA_SPEC ? 6 : 2;
   A.h = (double*)mp_ws(ctx, WS_IO1, sizeof(double) * nB * np * NPAR);
@@ -4440,11 +4484,15 @@ int mp_ha_plan(mp_ctx* ctx, const mp_ha_params* p, int32_t B, const double* star
   // with 12 / 6 / 4 (r05zg, r05zh); the 256-plan 24.0 ms with 6 or 4, 24.7 with 12; a 32-scene shard 16.4 ms with
   // 4 against 18.4-20.1 with 6, whose tail starts only at 28 live scenes, two blocks sharing each CU.
   const int per_ps = HA_PERSIST_PER((np + NBG_TAIL - 1) / NBG_TAIL);
-  const void* pfn[3] = {reinterpret_cast<const void*>(ha_persist_kernel<HW_TAIL, NBG_TAIL>),
-                        reinterpret_cast<const void*>(ha_persist_kernel<6, NBG_TAIL>),
-                        reinterpret_cast<const void*>(ha_persist_kernel<4, NBG_TAIL>)};
+  const void* pfn_rs[3] = {reinterpret_cast<const void*>(ha_persist_kernel<HW_TAIL, NBG_TAIL>),
+                           reinterpret_cast<const void*>(ha_persist_kernel<6, NBG_TAIL>),
+                           reinterpret_cast<const void*>(ha_persist_kernel<4, NBG_TAIL>)};
+  const void* pfn_as[3] = {reinterpret_cast<const void*>(ha_persist_kernel<HW_TAIL, NBG_TAIL, HA_SPEC, true>),
+                           reinterpret_cast<const void*>(ha_persist_kernel<6, NBG_TAIL, HA_SPEC, true>),
+                           reinterpret_cast<const void*>(ha_persist_kernel<4, NBG_TAIL, HA_SPEC, true>)};
+  const void* const* pfn = use_astar ? pfn_as : pfn_rs;  // (the use_astar instances look the table up)
   const int phws[3] = {HW_TAIL, 6, 4};
-  int* pcap = ctx->ha_pcap;  // co-resident blocks of each on this context's device (0: no cooperative launch)
+  int* pcap = use_astar ? ctx->ha_pcap_ast : ctx->ha_pcap;  // co-resident blocks of each on this context's device (0: no cooperative launch)
   int phw = 6;
   const void* persist_fn = pfn[1];
   double* rs_path2 = nullptr;
@@ -4523,8 +4571,12 @@ int mp_ha_plan(mp_ctx* ctx, const mp_ha_params* p, int32_t B, const double* star
       // the rest of the search in one cooperative launch, after the current nodes' expansion (bootstrap)
       const int per_pipe = 2 + (np + NBG_TAIL - 1) / NBG_TAIL;
       if (piped != 2) {
-        hipLaunchKernelGGL((ha_pipe_kernel<HW_TAIL, NBG_TAIL>), dim3((unsigned)(known * per_pipe)), dim3(64 * HW_TAIL),
-                           0, ctx->stream, D, Q, A, B, it, 1);
+        if (use_astar)
+          hipLaunchKernelGGL((ha_pipe_kernel<HW_TAIL, NBG_TAIL, true, true>), dim3((unsigned)(known * per_pipe)), dim3(64 * HW_TAIL),
+                             0, ctx->stream, D, Q, A, B, it, 1);
+        else
+          hipLaunchKernelGGL((ha_pipe_kernel<HW_TAIL, NBG_TAIL>), dim3((unsigned)(known * per_pipe)), dim3(64 * HW_TAIL),
+                             0, ctx->stream, D, Q, A, B, it, 1);
         piped = 2;
         piped_any = true;
       }
@@ -4553,29 +4605,53 @@ int mp_ha_plan(mp_ctx* ctx, const mp_ha_params* p, int32_t B, const double* star
     } else if (tail && tail_pipe && known * (2 + (np + NBG_TAIL - 1) / NBG_TAIL) <= pipe_blocks) {
       const int per_pipe = 2 + (np + NBG_TAIL - 1) / NBG_TAIL;
       if (piped != 2) {  // the current nodes' expansion, for the first pipelined launch
-        hipLaunchKernelGGL((ha_pipe_kernel<HW_TAIL, NBG_TAIL>), dim3((unsigned)(known * per_pipe)), dim3(64 * HW_TAIL),
-                           0, ctx->stream, D, Q, A, B, it, 1);
+        if (use_astar)
+          hipLaunchKernelGGL((ha_pipe_kernel<HW_TAIL, NBG_TAIL, true, true>), dim3((unsigned)(known * per_pipe)), dim3(64 * HW_TAIL),
+                             0, ctx->stream, D, Q, A, B, it, 1);
+        else
+          hipLaunchKernelGGL((ha_pipe_kernel<HW_TAIL, NBG_TAIL>), dim3((unsigned)(known * per_pipe)), dim3(64 * HW_TAIL),
+                             0, ctx->stream, D, Q, A, B, it, 1);
         piped = 2;
       }
-      hipLaunchKernelGGL((ha_pipe_kernel<HW_TAIL, NBG_TAIL>), dim3((unsigned)(known * per_pipe)), dim3(64 * HW_TAIL), 0,
-                         ctx->stream, D, Q, A, B, it, 0);
+      if (use_astar)
+        hipLaunchKernelGGL((ha_pipe_kernel<HW_TAIL, NBG_TAIL, true, true>), dim3((unsigned)(known * per_pipe)), dim3(64 * HW_TAIL), 0,
+                           ctx->stream, D, Q, A, B, it, 0);
+      else
+        hipLaunchKernelGGL((ha_pipe_kernel<HW_TAIL, NBG_TAIL>), dim3((unsigned)(known * per_pipe)), dim3(64 * HW_TAIL), 0,
+                           ctx->stream, D, Q, A, B, it, 0);
       piped_any = true;
     } else if (tail) {
       piped = 0;
       if (tail_rsh)  // + the prescan block per scene
-        hipLaunchKernelGGL((ha_step_kernel<HW_TAIL, NBG_TAIL, true>), dim3((unsigned)(known * (per_tail + 1))),
-                           dim3(64 * HW_TAIL), 0, ctx->stream, D, Q, A, B, it);
+        if (use_astar)
+          hipLaunchKernelGGL((ha_step_kernel<HW_TAIL, NBG_TAIL, true, true>), dim3((unsigned)(known * (per_tail + 1))),
+                             dim3(64 * HW_TAIL), 0, ctx->stream, D, Q, A, B, it);
+        else
+          hipLaunchKernelGGL((ha_step_kernel<HW_TAIL, NBG_TAIL, true>), dim3((unsigned)(known * (per_tail + 1))),
+                             dim3(64 * HW_TAIL), 0, ctx->stream, D, Q, A, B, it);
       else
-        hipLaunchKernelGGL((ha_step_kernel<HW_TAIL, NBG_TAIL>), dim3((unsigned)(known * per_tail)),
-                           dim3(64 * HW_TAIL), 0, ctx->stream, D, Q, A, B, it);
+        if (use_astar)
+          hipLaunchKernelGGL((ha_step_kernel<HW_TAIL, NBG_TAIL, false, true>), dim3((unsigned)(known * per_tail)),
+                             dim3(64 * HW_TAIL), 0, ctx->stream, D, Q, A, B, it);
+        else
+          hipLaunchKernelGGL((ha_step_kernel<HW_TAIL, NBG_TAIL>), dim3((unsigned)(known * per_tail)),
+                             dim3(64 * HW_TAIL), 0, ctx->stream, D, Q, A, B, it);
     } else if (known * per <= mid_blocks) {
       piped = 0;
-      hipLaunchKernelGGL((ha_step_kernel<HA_MID_HW, NBG>), dim3((unsigned)(known * per)),
-                         dim3(64 * HA_MID_HW), 0, ctx->stream, D, Q, A, B, it);
+      if (use_astar)
+        hipLaunchKernelGGL((ha_step_kernel<HA_MID_HW, NBG, false, true>), dim3((unsigned)(known * per)),
+                           dim3(64 * HA_MID_HW), 0, ctx->stream, D, Q, A, B, it);
+      else
+        hipLaunchKernelGGL((ha_step_kernel<HA_MID_HW, NBG>), dim3((unsigned)(known * per)),
+                           dim3(64 * HA_MID_HW), 0, ctx->stream, D, Q, A, B, it);
     } else {
       piped = 0;
-      hipLaunchKernelGGL((ha_step_kernel<HW, NBG>), dim3((unsigned)(known * per)), dim3(HT), 0,
-                         ctx->stream, D, Q, A, B, it);
+      if (use_astar)
+        hipLaunchKernelGGL((ha_step_kernel<HW, NBG, false, true>), dim3((unsigned)(known * per)), dim3(HT), 0,
+                           ctx->stream, D, Q, A, B, it);
+      else
+        hipLaunchKernelGGL((ha_step_kernel<HW, NBG>), dim3((unsigned)(known * per)), dim3(HT), 0,
+                           ctx->stream, D, Q, A, B, it);
     }
     if (hipGetLastError() != hipSuccess) { cleanup(); return mp_fail(ctx, MP_ERR_HIP, "ha kernel launch failed"); }
     // (Measured and removed: polling the live count every 4 iterations near the persistent tail's threshold,
@@ -4667,7 +4743,7 @@ int mp_ha_plan(mp_ctx* ctx, const mp_ha_params* p, int32_t B, const double* star
     if (found[b])
       std::copy(rsb.begin() + (size_t)b * max_rs * 3, rsb.begin() + ((size_t)b * max_rs + rs_len[b]) * 3,
                 rs_path + (size_t)b * MAXPATH * 3);
-  return MP_OK;
+  return use_astar ? mp_as_table_status(ctx) : MP_OK;
 }
 
 }  // extern "C"

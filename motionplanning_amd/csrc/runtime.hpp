@@ -57,7 +57,13 @@ struct mp_ctx {
   // (a context is used by one thread at a time, so the flags need no lock)
   bool mppi_lds_attr = false, fin_lds_attr = false;
   bool ilqr_fused_attr = false;  // the fused iLQR backward kernel's dynamic-LDS attribute is set
-  int ha_pcap[3] = {-1, -1, -1};  // co-resident blocks of each ha_persist_kernel shape on this device (0: none)
+  bool astar_lds_attr = false;  // as_search_kernel's dynamic-LDS attribute is set
+  // host copies of the grid A* table's per-scene geometry (they outlive the asynchronous uploads)
+  std::vector<double> as_geo_host;
+  std::vector<int> as_gcell_host;
+  double as_hdr_host[3] = {0, 0, 0};  // mp_ha_plan_astar's table header (address bits, x_factor, y_factor)
+  int ha_pcap[3] = {-1, -1, -1};
+  int ha_pcap_ast[3] = {-1, -1, -1};  // ... of the use_astar instances  // co-resident blocks of each ha_persist_kernel shape on this device (0: none)
   // multi-GPU in one process (mp_comm_init): the group and this context's rank in it
   mp_comm_group* comm = nullptr;
   int comm_rank = -1;
@@ -110,6 +116,14 @@ enum {
   WS_FIN_END = WS_FIN0 + MP_FIN_RING - 1,
   WS_SHARD_SEND,  // mp_mppi_plan_sharded: this rank's packed per-scene results
   WS_SHARD_RECV,  // ... and every rank's, after the all-gather
+  WS_AS_GEO,      // grid A* (astar.hip): per-scene origin and factors
+  WS_AS_GCELL,    // ... goal cells
+  WS_AS_SCELL,    // ... start cells
+  WS_AS_OBS,      // ... obstacles
+  WS_AS_WALL,     // ... block corner points
+  WS_AS_MASK,     // ... free-cell masks
+  WS_AS_TABLE,    // ... mp_astar_plan's outputs / the Hybrid A* heuristic table
+  WS_AS_ERR,      // ... pop-cap flag
   WS_COUNT
 };
 
@@ -128,6 +142,12 @@ int mp_ticket_reserve(mp_ctx* ctx, int n);
 void* mp_pinned(mp_ctx* ctx, size_t bytes);
 // 8 words of coherent host memory (host pointer; *dev = the device's address of it), nullptr on failure
 unsigned long long* mp_mapped(mp_ctx* ctx, unsigned long long** dev);
+
+// astar.hip: Hybrid A*'s astar_heuristic table for B scenes, enqueued on the context stream (goal on the
+// host, walls on the device; *table_dev = [B][121]); mp_as_table_status synchronises and reports a pop cap
+int mp_as_table_dev(mp_ctx* ctx, const mp_ha_params* p, int B, const double* goal, const double* walls_dev,
+                    const double** table_dev);
+int mp_as_table_status(mp_ctx* ctx);
 
 #define MP_HIP(ctx, call)                                                                \
   do {                                                                                   \

@@ -114,9 +114,8 @@ class HybridAstarSearcher:
 def defineHybridAstar(vehicle_size=(2, 1), gear_set=(1, -1), steer_set=None, minR=1.0, expand_time=1.0,
                       resolutions=(0.2, 0.2, PI / 10), stbound=((-15, 15), (-15, 5), (-PI, PI)),
                       starting_real=(10.0, -5.0, 0.0), ending_real=(-5.0, -5.0, 0.0), use_astar=False):
-    """setup.jl:3-53.  use_astar=True (the grid-A* heuristic) is out of scope (SURVEY §2 #7)."""
-    if use_astar:
-        raise NotImplementedError("use_astar=true (PathPlanning/Astar heuristic) is out of scope")
+    """setup.jl:3-53.  use_astar=True adds the grid-A* heuristic (astar_heuristic, hybrid_astar_utils.jl:375-387):
+    the planner then runs mp_ha_plan_astar with its per-scene 11 x 11 table."""
     steer_set = julia_linrange(-1, 1, 7) if steer_set is None else np.asarray(steer_set, np.float64)
     h = HybridAstarSearcher()
     s = h.s
@@ -134,6 +133,7 @@ def defineHybridAstar(vehicle_size=(2, 1), gear_set=(1, -1), steer_set=None, min
     s.starting_states = regulate_states(s.resolutions, s.starting_real)
     s.ending_states = regulate_states(s.resolutions, s.ending_real)
     s.n_col = int(math.floor(s.expand_time / 1e-2))
+    s.use_astar = bool(use_astar)
     return h
 
 
@@ -173,17 +173,20 @@ def install_primitives(h, ctx=None):
 def plan_batch(searchers, ctx=None, max_pops=5000):
     """planHybridAstar! for B scenes sharing settings (vehicle, primitives, bounds, resolutions,
     number of walls), each with its own start, goal and walls, in lockstep on the device."""
-    ctx = ctx or default_context()
     h0 = searchers[0]
     p = params_of(h0, max_pops)
+    if any(len(h.s.obstacle_list) != p.n_walls for h in searchers):
+        raise ValueError("plan_batch: every scene needs the same number of walls")
+    use_astar = bool(h0.s.use_astar)
+    if any(bool(h.s.use_astar) != use_astar for h in searchers):
+        raise ValueError("plan_batch: every scene needs the same use_astar")
+    ctx = ctx or default_context()
     # the primitive table (the library keeps it while the settings stay the same; no copies back)
     ctx.check(ctx.lib.mp_ha_neighbor_origin(ctx.handle, ctypes.byref(params_of(h0)), h0.s.num_steer, ptr(h0.s.steer_set),
                                             h0.s.num_gear, ptr(h0.s.gear_set), None, None))
     B = len(searchers)
     start = f64([h.s.starting_states for h in searchers])
     goal = f64([h.s.ending_states for h in searchers])
-    if any(len(h.s.obstacle_list) != p.n_walls for h in searchers):
-        raise ValueError("plan_batch: every scene needs the same number of walls")
     walls = np.fromiter(itertools.chain.from_iterable(itertools.chain.from_iterable(h.s.obstacle_list for h in searchers)),
                         np.float64, B * p.n_walls * 5).reshape(B, p.n_walls, 5)
     found = np.zeros(B, np.int32)
@@ -200,9 +203,14 @@ def plan_batch(searchers, ctx=None, max_pops=5000):
         ctx._ha_plan_bufs = bufs
     _, pop_seq, states, rs_path = bufs
     t0 = time.time()
-    ctx.check(ctx.lib.mp_ha_plan(ctx.handle, ctypes.byref(p), B, ptr(start), ptr(goal), ptr(walls), ptr(found),
-                                 ptr(pops), ptr(n_nodes), ptr(pop_seq), ptr(n_states), ptr(states), ptr(rs_len),
-                                 ptr(rs_path)))
+    if use_astar:
+        ctx.check(ctx.lib.mp_ha_plan_astar(ctx.handle, ctypes.byref(p), B, ptr(start), ptr(goal), ptr(walls), 1,
+                                           ptr(found), ptr(pops), ptr(n_nodes), ptr(pop_seq), ptr(n_states),
+                                           ptr(states), ptr(rs_len), ptr(rs_path)))
+    else:
+        ctx.check(ctx.lib.mp_ha_plan(ctx.handle, ctypes.byref(p), B, ptr(start), ptr(goal), ptr(walls), ptr(found),
+                                     ptr(pops), ptr(n_nodes), ptr(pop_seq), ptr(n_states), ptr(states), ptr(rs_len),
+                                     ptr(rs_path)))
     dt = time.time() - t0
     # one compact copy per output, each scene's result a view of it (nothing aliases the reused buffers)
     ps = pop_seq[:, : max(int(pops.max()), 0)].copy()
@@ -323,16 +331,16 @@ PARALLEL = dict(  # main_hybrid_astar.jl:10-12
            [(5.5 + 3) / 2, 1.0, 0.0, 1.0, 1.0]])
 
 
-def driver_searcher(scene=PERPENDICULAR, start=None):
+def driver_searcher(scene=PERPENDICULAR, start=None, use_astar=False):
     st = driver_settings()
     h = defineHybridAstar(st["vehicle_size"], st["gear_set"], st["steer_set"], st["minR"], st["expand_time"],
                           st["resolutions"], st["stbound"], scene["starting_real"] if start is None else start,
-                          scene["ending_real"])
+                          scene["ending_real"], use_astar)
     defineHybridAstarobs_(h, scene["walls"])
     return h
 
 
-def scenario_batch(n=256, seed=4):
+def scenario_batch(n=256, seed=4, use_astar=False):
     """n/2 perpendicular + n/2 parallel scenes; start x in {5, 5.5, ..., 9},
     start ψ = π/2 + k·π/12, k in {-2..2}, seeded."""
     r = np.random.default_rng(seed)
@@ -342,5 +350,5 @@ def scenario_batch(n=256, seed=4):
         scene = PERPENDICULAR if i < n // 2 else PARALLEL
         x = float(xs[r.integers(len(xs))])
         k = int(r.integers(-2, 3))
-        out.append(driver_searcher(scene, [x, 0.0, PI / 2 + k * PI / 12]))
+        out.append(driver_searcher(scene, [x, 0.0, PI / 2 + k * PI / 12], use_astar))
     return out
