@@ -448,6 +448,60 @@ int mp_astar_plan(mp_ctx* ctx, int32_t B, int32_t nx, int32_t ny, const double* 
                   double* final_cost, int32_t* found, int32_t* pops, int32_t* n_nodes, int32_t* pop_seq,
                   int32_t* astarpath, int32_t* path_n, double* path_length);
 
+/* ----------------------------------------------------------- RRT / RRT* */
+#define MP_RRT_MAX_ITER 1000000 /* cap on n_iter (the tree workspace is 48 bytes per node and scene) */
+
+/* Settings mirror RRTSettings (PathPlanning/RRT/src/types.jl:19-39). */
+typedef struct mp_rrt_params {
+  int32_t n_iter;        /* sampling_number; 1 .. MP_RRT_MAX_ITER               */
+  int32_t buffer_size;   /* nodes registered between BallTree rebuilds; >= 1    */
+  int32_t rrt_star;      /* 0: RRT, 1: RRT* (near set + rewire)                 */
+  int32_t reserved;
+  double bias_rate, grow_min, grow_max, goal_tolerance; /* grow_dist = [grow_min, grow_max] */
+} mp_rrt_params;
+/* Alias of mp_rrt_params, the name mp_rrt_plan's prototype uses; the two are one type. */
+typedef mp_rrt_params mp_rrt_params_t;
+
+/*
+ * mp_rrt_plan — planRRT! (PathPlanning/RRT/src/rrt_utils.jl:341-412) for B independent scenes in one
+ * launch, one workgroup per scene, the whole sampling loop on the device: sampleRRT (:18-39), the nearest
+ * node of the BallTree snapshot (rebuilt every buffer_size registered nodes, :386-389 -- between rebuilds
+ * the newer nodes are not seen, as in the reference), steer (:159-191) with ProjectionStates (:112-134),
+ * collision (:282-311: the bound test on the new point, then both end points against every circle with <=),
+ * registerNode, and with rrt_star the near set (:374-377), rewire (:216-238, root_idx = min_idx) and
+ * costPropogation (:240-268); then findBestIdx (:414-422) over all nodes and getBestIdxs.
+ * in : bound[B][4] (BoundPosition: xmin, xmax, ymin, ymax), start[B][2], goal[B][2],
+ *      obstacles[B][n_obs][3] circles [x, y, r]; obs_count[B] (NULL: n_obs each) circles of scene b that
+ *      count, the rest of its rows is padding and is not read; n_obs = 0: no obstacles,
+ *      uniforms[B][n_iter][3]: (u_bias, u_x, u_y) in [0, 1) per iteration.  The library draws no random
+ *      numbers: u_bias < bias_rate makes the sample the goal (u_x, u_y ignored, where the reference does
+ *      not draw them), otherwise it is (u_x*(xmax-xmin)+xmin, u_y*(ymax-ymin)+ymin).
+ * out: n_nodes[B] (sample_idx), status[B] (1 :Solved, 0 :NotSolved), best_idx[B] (0 when not solved),
+ *      best_cost[B] (costs_collection[best_idx]; 0.0 when not solved).
+ * optional (NULL: not returned), node i (1-based, as the reference) in row i - 1, rows past n_nodes zero:
+ *      loc[B][n_iter+1][2], cost[B][n_iter+1], parent[B][n_iter+1] (node 1: -1),
+ *      path_idx[B][n_iter+1] with path_n[B] (both or neither): getBestIdxs, goal side first, ending in 1,
+ *      counters[B][4]: samples rejected by collision, rewired edges, near sets that reached the cap of
+ *      100, steers that took the in-range branch.
+ * Defined differently from the reference:
+ *   - tree queries: NearestNeighbors' knn / inrange (their tie order and the last-ulp pruning of their
+ *     trees) are brute force over the same nodes: the nearest node is the minimum of dx*dx + dy*dy, the
+ *     lowest index on ties; the near set is every snapshot node with sqrt(dx*dx + dy*dy) <= r, and from
+ *     100 such nodes on the 100 nearest by (distance, index); the goal set is dx*dx + dy*dy <=
+ *     goal_tolerance^2, minimum cost, lowest index on ties;
+ *   - nearDisk's ^(0.5) is sqrt;
+ *   - the 100 s wall-clock break (:391-394) is dropped: all n_iter samples are drawn;
+ *   - node capacity: the reference's arrays hold sampling_number nodes and it writes node
+ *     sampling_number + 1 out of bounds when every sample registers; here the capacity is n_iter + 1.
+ * round(v, digits = 2) is rint(v*100.0)/100.0 and norm of a 2-vector is sqrt(v1*v1 + v2*v2).
+ * n_iter outside 1 .. MP_RRT_MAX_ITER, buffer_size < 1 and non-finite bounds, start or goal return
+ * MP_ERR_INVALID before anything is launched. */
+int mp_rrt_plan(mp_ctx* ctx, const mp_rrt_params_t* p, int32_t B, const double* bound, const double* start,
+                const double* goal, int32_t n_obs, const int32_t* obs_count, const double* obstacles,
+                const double* uniforms, int32_t* n_nodes, int32_t* status, int32_t* best_idx, double* best_cost,
+                double* loc, double* cost, int32_t* parent, int32_t* path_idx, int32_t* path_n,
+                int32_t* counters);
+
 /* ------------------------------------------------------- path tracker */
 /* Settings of the Hybrid A* path tracker (PathPlanning/HybridAstar/main_Tracker.jl:42-72). */
 typedef struct mp_track_params {

@@ -29,7 +29,7 @@ module MPGPU
 using Interpolations: interpolate, Gridded, Constant, Previous, linear_interpolation   # as the reference drivers
 
 export MPPIPlan, MPPIClosedLoop, planHybridAstar!, mppi_plan_batch, mppi_plan_sharded, comm_init, mppi_closed_loop_batch,
-       rollout_batch, ha_expand, ha_rs_connect, ha_astar_table, astar_plan_batch,
+       rollout_batch, ha_expand, ha_rs_connect, ha_astar_table, astar_plan_batch, rrt_plan_batch,
        ha_allpath, ha_neighbor_origin, retrieve_batch!, track_batch!, ilqr_rollout, ilqr_backward!, ilqr_forward!,
        ilqr_solve!, vehicle_euler!, ctx_join
 
@@ -498,6 +498,47 @@ function astar_plan_batch(mapbound, bound::Matrix{Float64}, start_real::Matrix{F
         plen), c)
     return (; final_cost = cost, found, loop_count = pops, n_nodes = nn, pop_sequence = seq, astarpath = path,
             path_n = pn, path_length = plen)
+end
+
+struct RrtParams     # mp_rrt_params (PathPlanning/RRT/src/types.jl:19-39)
+    n_iter::Int32
+    buffer_size::Int32
+    rrt_star::Int32
+    reserved::Int32
+    bias_rate::Float64
+    grow_min::Float64
+    grow_max::Float64
+    goal_tolerance::Float64
+end
+
+"""
+    rrt_plan_batch(p, bound, start, goal, obstacles, uniforms; obs_count = nothing)
+
+planRRT! (PathPlanning/RRT/src/rrt_utils.jl:341-412) for B scenes in one launch (mp_rrt_plan): bound (4, B) =
+BoundPosition, start / goal (2, B), obstacles (3, n_obs, B) circles with `obs_count[b]` of them counting (nothing:
+all), uniforms (3, n_iter, B) = (u_bias, u_x, u_y) per iteration, e.g. `rand(3, p.n_iter, B)`.  Returns n_nodes,
+status (1 = :Solved), best_idx, best_cost, the tree (loc (2, n_iter+1, B), cost, parent; 1-based node indices,
+parent of node 1 is -1), the best path's indices (goal side first, `path_n[b]` of them) and the four counters
+(rejected samples, rewired edges, capped near sets, in-range steers).
+"""
+function rrt_plan_batch(p::RrtParams, bound::Matrix{Float64}, start::Matrix{Float64}, goal::Matrix{Float64},
+                        obstacles::Array{Float64,3}, uniforms::Array{Float64,3}; obs_count = nothing)
+    B = size(bound, 2); cap = Int(p.n_iter) + 1
+    n_obs = size(obstacles, 2)
+    size(uniforms) == (3, Int(p.n_iter), B) || error("rrt_plan_batch: uniforms must be (3, n_iter, B)")
+    oc = obs_count === nothing ? Int32[] : Vector{Int32}(obs_count)
+    nn = zeros(Int32, B); status = zeros(Int32, B); best = zeros(Int32, B); bcost = zeros(B)
+    loc = zeros(2, cap, B); cost = zeros(cap, B); parent = zeros(Int32, cap, B)
+    path = zeros(Int32, cap, B); pn = zeros(Int32, B); counters = zeros(Int32, 4, B)
+    c = ctx()
+    check(GC.@preserve bound start goal obstacles uniforms oc nn status best bcost loc cost parent path pn counters ccall((:mp_rrt_plan, libmpgpu), Cint,
+        (Ptr{Cvoid}, Ref{RrtParams}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Int32}, Ptr{Float64},
+         Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32},
+         Ptr{Int32}, Ptr{Int32}, Ptr{Int32}),
+        c, p, B, bound, start, goal, n_obs, obs_count === nothing ? C_NULL : pointer(oc), obstacles, uniforms, nn, status,
+        best, bcost, loc, cost, parent, path, pn, counters), c)
+    return (; n_nodes = nn, status, best_idx = best, best_cost = bcost, loc, cost, parent, path_idx = path, path_n = pn,
+            counters)
 end
 
 """

@@ -137,6 +137,23 @@ class TrackParams(ctypes.Structure):
     ]
 
 
+class RRTParams(ctypes.Structure):
+    """mp_rrt_params (include/mpgpu.h) — RRTSettings, PathPlanning/RRT/src/types.jl:19-39."""
+
+    _fields_ = [
+        ("n_iter", ctypes.c_int32),
+        ("buffer_size", ctypes.c_int32),
+        ("rrt_star", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("bias_rate", ctypes.c_double),
+        ("grow_min", ctypes.c_double),
+        ("grow_max", ctypes.c_double),
+        ("goal_tolerance", ctypes.c_double),
+    ]
+
+
+MP_RRT_MAX_ITER = 1000000
+
 MP_TRACK_DONE = 0
 MP_TRACK_MAXSTEP = 1
 MP_TRACK_NOPATH = 2
@@ -182,6 +199,7 @@ SIGNATURES = {
     "mp_ha_plan_astar": (ctypes.c_int, [_V, ctypes.POINTER(HAParams), _I, _V, _V, _V, _I] + [_V] * 8),
     "mp_ha_astar_table": (ctypes.c_int, [_V, ctypes.POINTER(HAParams), _I, _V, _V, _V]),
     "mp_astar_plan": (ctypes.c_int, [_V, _I, _I, _I, _V, _V, _V, _I, _I] + [_V] * 9),
+    "mp_rrt_plan": (ctypes.c_int, [_V, ctypes.POINTER(RRTParams), _I, _V, _V, _V, _I] + [_V] * 13),
     "mp_ha_retrieve_path": (ctypes.c_int, [_V, _I, _V, _V, _V, _I] + [_V] * 8),
     "mp_ha_track": (ctypes.c_int, [_V, ctypes.POINTER(TrackParams), _I, _V, _V, _V, _I] + [_V] * 6 + [_I]),
     "mp_math_eval": (ctypes.c_int, [_V, _I, ctypes.c_int64, _V, _V, _V]),
