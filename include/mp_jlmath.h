@@ -717,6 +717,94 @@ __device__ __forceinline__ double mpj_sel(int c, double t, double f) {
 #define MPJ_SEL(c, t, f) ((c) ? (t) : (f))
 #endif
 
+/* ------------------------------------------------------- exact cheap divisions */
+/* `n / d` is the definition; the device forms below are an optimisation of it that gives the same bits.
+ * hipcc expands an f64 `/` into v_div_scale (divisor), v_div_scale (numerator), v_rcp_f64, four FMAs
+ * refining the reciprocal, q = n·y, e = fma(-d, q, n), v_div_fmas (fma(e, y, q), rescaled when VCC),
+ * v_div_fixup: 11 instructions.  v_div_scale_f64 returns its operand unchanged, with VCC clear, unless
+ * (ISA: V_DIV_SCALE_F64) an operand is zero, the divisor is subnormal, exp(n) - exp(d) >= 768, 1/d or n/d
+ * is subnormal (exp(d) >= 2045, exp(n) - exp(d) <= -1023), or exp(n) <= 53 (biased exponents); v_div_fixup
+ * changes the result only for zero, Inf and NaN operands and for quotients beyond the exponent range.
+ * Outside those cases the expansion is exactly
+ *     y = mpj_rcp_nr(d);  q = n·y;  e = fma(-d, q, n);  n / d = fma(e, y, q)            (mpj_div_r)
+ * and the five instructions of y depend on d alone: a divisor that never changes, or that two
+ * numerators share, pays for them once.
+ *
+ * The window W: biased exponent in [0x280, 0x57f], i.e. 2^-383 <= |x| < 2^385.  With n and d both in W
+ * none of the scaling cases can hold (|exp(n) - exp(d)| <= 767, both normal, exp(n) > 53), n/d is a normal
+ * finite nonzero number, and mpj_div_r(n, d, y) == n / d bit for bit.  mpj_div_out is the guard: zero,
+ * subnormal, Inf and NaN all lie outside W (conservative: W is narrower than the no-scaling region;
+ * tests/test_gpu_mppi_diet.py compares the guard with what v_div_scale_f64 does on the device). */
+MPJ_FN uint32_t mpj_div_key(double x) { return mpj_hi(x) & 0x7fffffffu; }
+#define MPJ_DIV_WLO 0x28000000u
+#define MPJ_DIV_WHI 0x58000000u
+MPJ_FN int mpj_div_out(double x) { return (mpj_div_key(x) - MPJ_DIV_WLO) >= (MPJ_DIV_WHI - MPJ_DIV_WLO); }
+/* v_rcp_f64 and the same four FMAs, in the same order, as the compiler's expansion applies to the
+ * (unscaled) divisor.  Host: a placeholder, mpj_div_r ignores it. */
+MPJ_FN double mpj_rcp_nr(double d) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  double y = __builtin_amdgcn_rcp(d);
+  double f = __builtin_fma(-d, y, 1.0);
+  y = __builtin_fma(y, f, y);
+  f = __builtin_fma(-d, y, 1.0);
+  return __builtin_fma(y, f, y);
+#else
+  return 1.0 / d;
+#endif
+}
+/* n / d given y = mpj_rcp_nr(d), for n and d where the expansion neither scales nor fixes up. */
+MPJ_FN double mpj_div_r(double n, double d, double y) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const double q = n * y;
+  const double e = __builtin_fma(-d, q, n);
+  return __builtin_fma(e, y, q);
+#else
+  (void)y;
+  return n / d;
+#endif
+}
+/* mpj_div_r followed by the expansion's own v_div_fixup: also right for zero, Inf and NaN operands
+ * (where the fixup ignores the quotient it is handed).  Nonzero finite operands must still be such
+ * that the expansion does not scale. */
+MPJ_FN double mpj_div_rf(double n, double d, double y) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_div_fixup(mpj_div_r(n, d, y), d, n);
+#else
+  (void)y;
+  return n / d;
+#endif
+}
+/* Guarded forms (any n, any d): the whole wave takes plain `/` when some lane's operand is outside W. */
+MPJ_FN double mpj_div_g(double n, double d) {
+  if (MPJ_ANY(mpj_div_out(n) | mpj_div_out(d))) return n / d;
+  return mpj_div_r(n, d, mpj_rcp_nr(d));
+}
+/* y = mpj_rcp_nr(d) kept by the caller; d_ok: it has checked once that d is in W (a constant, or a launch constant) */
+MPJ_FN double mpj_div_gn(double n, double d, double y, int d_ok) {
+  if (MPJ_ANY(mpj_div_out(n) | !d_ok)) return n / d;
+  return mpj_div_r(n, d, y);
+}
+/* zero, Inf and NaN numerators go through the fixup instead of the guard; d in W (d_ok) */
+MPJ_FN double mpj_div_gf(double n, double d, double y, int d_ok) {
+  const uint32_t k = mpj_div_key(n) | (mpj_lo(n) != 0);
+  if (MPJ_ANY(((k != 0) & (k < 0x7ff00000u) & mpj_div_out(n)) | !d_ok)) return n / d;
+  return mpj_div_rf(n, d, y);
+}
+/* n1 / d and n2 / d over one reciprocal */
+MPJ_FN void mpj_div2_g(double n1, double n2, double d, double* q1, double* q2) {
+  const uint32_t a = mpj_div_key(n1), b = mpj_div_key(n2), c = mpj_div_key(d);
+  const uint32_t ab0 = a < b ? a : b, ab1 = a < b ? b : a;
+  const uint32_t mn = ab0 < c ? ab0 : c, mx = ab1 < c ? c : ab1;
+  if (MPJ_ANY((mn < MPJ_DIV_WLO) | (mx >= MPJ_DIV_WHI))) {
+    *q1 = n1 / d;
+    *q2 = n2 / d;
+    return;
+  }
+  const double y = mpj_rcp_nr(d);
+  *q1 = mpj_div_r(n1, d, y);
+  *q2 = mpj_div_r(n2, d, y);
+}
+
 MPJ_FN double mpj_atan_bl(double x) {
   const double aT0 = 3.33333333333329318027e-01, aT1 = -1.99999999998764832476e-01,
                aT2 = 1.42857142725034663711e-01, aT3 = -1.11111104054623557880e-01,
@@ -788,6 +876,67 @@ MPJ_FN double mpj_atan_tab(double x, const double* tab) {
    * before the sign flip: FDLIBM's -atanhi[3] - atanlo[3] is exactly -(atanhi[3] + atanlo[3]). */
   const double big = 1.57079632679489655800e+00 + 6.12323399573676603587e-17;
   return mpj_flip(MPJ_SEL(ix >= 0x44100000u && x == x, big, r), hx & 0x80000000u);
+}
+
+/* mpj_atan_tab with the range row fetched directly: FDLIBM's four range thresholds 0x3fdc0000,
+ * 0x3fe60000, 0x3ff30000, 0x40038000 (high words of 0.4375, 0.6875, 1.1875, 2.4375) are all multiples
+ * of 0x8000, so b = ix >> 15 clamped to [0x7fb7, 0x8007] decides the range: b = 0x7fb7 is range 0,
+ * 0x7fb8..0x7fcb range 1, 0x7fcc..0x7fe5 range 2, 0x7fe6..0x8006 range 3, 0x8007 range 4.  The table has
+ * one {na, nb, hi, lo} row per b (81 rows, 2592 bytes; LDS on the device), replacing the four compares
+ * and adds of the range index.
+ *
+ * The reduction (na·a - nb) / (na + nb·a) needs neither guard nor fixup (mpj_rcp_nr / mpj_div_r above)
+ * for every input whose quotient is used, |x| < 2^66:
+ *   range 0: a / 1 with y = 1 exactly: q = a, e = fma(-1, a, a) = +0, fma(+0, 1, a) = a for every
+ *            a >= +0, subnormals and +0 included, where plain `/` gives a as well;
+ *   ranges 1-3: a in [0.4375, 2.4375), the numerator 2a - 1, a - 1 or a - 1.5 is +0 (0.5, 1, 1.5: an exact
+ *            difference rounds to +0, and the form gives q = +0·y = +0, e = +0, +0 — what the fixup of
+ *            `/` gives for +0 over a positive divisor) or a multiple of 2^-53 with |.| in [2^-53, 2.875],
+ *            the divisor 2 + a, 1 + a or 1 + 1.5a lies in [1.6875, 4.66];
+ *   range 4: -1 / a, a in [2.4375, 2^66).
+ * All nonzero operands are inside W.  For |x| >= 2^66 and ±Inf the quotient is replaced by the `big`
+ * select; NaN gives NaN in both forms (every operand is the same quieted NaN). */
+#define MPJ_ATAN_ROWS 81
+#define MPJ_ATAN_ROW0 0x7fb7u
+/* rows i0, i0 + step, ... of rows[4 * MPJ_ATAN_ROWS] (a thread block fills the table with i0 = its thread
+ * index and step = its size); the constants are mpj_atan_tab_init's, picked by constant index */
+MPJ_FN void mpj_atan_rows_fill(double* rows, uint32_t i0, uint32_t step) {
+  double t[20];
+  mpj_atan_tab_init(t);
+  for (uint32_t i = i0; i < MPJ_ATAN_ROWS; i += step) {
+    const uint32_t ix = (MPJ_ATAN_ROW0 + i) << 15; /* a high word of row i (all of a row share the range) */
+    for (int j = 0; j < 4; j++)
+      rows[4 * i + j] = ix >= 0x40038000u ? t[16 + j] : ix >= 0x3ff30000u ? t[12 + j] : ix >= 0x3fe60000u ? t[8 + j]
+                      : ix >= 0x3fdc0000u ? t[4 + j] : t[j];
+  }
+}
+MPJ_FN void mpj_atan_rows_init(double* rows) { mpj_atan_rows_fill(rows, 0, 1); }
+MPJ_FN double mpj_atan_rows(double x, const double* rows) {
+  const double aT0 = 3.33333333333329318027e-01, aT1 = -1.99999999998764832476e-01,
+               aT2 = 1.42857142725034663711e-01, aT3 = -1.11111104054623557880e-01,
+               aT4 = 9.09088713343650656196e-02, aT5 = -7.69187620504482999495e-02,
+               aT6 = 6.66107313738753120669e-02, aT7 = -5.83357013379057348645e-02,
+               aT8 = 4.97687799461593236017e-02, aT9 = -3.65315727442169155270e-02,
+               aT10 = 1.62858201153657823623e-02;
+  const uint32_t hx = mpj_hi(x);
+  const uint32_t ix = hx & 0x7fffffffu;
+  const uint32_t b0 = ix >> 15;
+  const uint32_t b1 = b0 < MPJ_ATAN_ROW0 ? MPJ_ATAN_ROW0 : b0;
+  const uint32_t b = b1 > MPJ_ATAN_ROW0 + MPJ_ATAN_ROWS - 1 ? MPJ_ATAN_ROW0 + MPJ_ATAN_ROWS - 1 : b1;
+  const double a = mpj_fabs(x);
+  const double* t = rows + 4 * (b - MPJ_ATAN_ROW0);
+  const double na = t[0], nb = t[1], hi = t[2], lo = t[3];
+  const double dn = na + nb * a;
+  const double ax = mpj_div_r(na * a - nb, dn, mpj_rcp_nr(dn));
+  const double z = ax * ax;
+  const double w = z * z;
+  const double s1 = z * mpj_fma(w, mpj_fma(w, mpj_fma(w, mpj_fma(w, mpj_fma(w, aT10, aT8), aT6), aT4), aT2), aT0);
+  const double s2 = w * mpj_fma(w, mpj_fma(w, mpj_fma(w, mpj_fma(w, aT9, aT7), aT5), aT3), aT1);
+  const double r = hi - ((ax * (s1 + s2) - lo) - ax);
+  /* as mpj_atan_tab, with its tests in their cheapest form: ix >= 0x44100000 and not NaN is a >= 2^66 (false
+   * for NaN), and the flip of a result that carries no sign (r >= +0, big > 0; NaN aside) is a copysign */
+  const double big = 1.57079632679489655800e+00 + 6.12323399573676603587e-17;
+  return __builtin_copysign(MPJ_SEL(a >= 0x1p66, big, r), x);
 }
 
 /* mpj_atan2 with the branch-free atan core (bit-identical: mpj_atan_bl == mpj_atan). */
@@ -966,7 +1115,10 @@ MPJ_FN double mpj_log_bl(double x) {
   const int32_t i0 = (hm + 0x95f64) & 0x100000;
   const int32_t k = (hx0 >> 20) - 1023 + (i0 >> 20);
   const double f = mpj_from_words((uint32_t)(hm | (i0 ^ 0x3ff00000)), mpj_lo(x)) - 1.0;
-  const double s = f / (2.0 + f);
+  /* f / (2 + f) without guard or fixup (mpj_div_r): past the test above 2^-20 <= |f| < 0.42 and
+   * 2 + f lies in [1.7, 2.42], both inside the no-scaling window, neither zero, Inf nor NaN */
+  const double f2 = 2.0 + f;
+  const double s = mpj_div_r(f, f2, mpj_rcp_nr(f2));
   const double dk = (double)k;
   const double z = s * s;
   const double w = z * z;

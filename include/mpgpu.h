@@ -551,8 +551,12 @@ int mp_ha_track(mp_ctx* ctx, const mp_track_params* p, int32_t B, const double* 
  * 4 atan2(x, y), 5 asin, 6 acos, 7 exp, 8 log, 9 modpi, 10 sqrt; the branch-free
  * variants of the hot kernels: 11 modpi_bl, 12 atan_bl, 13 atan_tab, 14 sin (sincos_bl),
  * 15 cos (sincos_bl), 16 exp_fdlibm, 17 tan_bl, 18 atan2_sel(x, y), 19 sin / 20 cos (sincos_wide),
- * 21 tan_wide, 22 sin_34 (tyre sin, |x| <= 3π/4 fast path), 23 log_bl — each must equal its exact
- * routine bit for bit. */
+ * 21 tan_wide, 22 sin_34 (tyre sin, |x| <= 3π/4 fast path), 23 log_bl, 24 atan_rows — each must equal its
+ * exact routine bit for bit.  The exact cheap divisions x / y, each equal to `/` bit for bit: 25 div_g
+ * (guarded), 26 div_gn (hoisted reciprocal, divisor window checked by the caller), 27 div_gf (the same with
+ * the fixup taking zero, Inf and NaN numerators), 28 / 29 the first / second quotient of the
+ * shared-reciprocal pair div2_g (x, 1) / y and (-1.5, x) / y.  30: what v_div_scale_f64 does to x / y, as
+ * 1·(numerator changed) + 2·(divisor changed) + 4·(VCC set), to check the guard's window against. */
 int mp_math_eval(mp_ctx* ctx, int32_t fn, int64_t n, const double* x, const double* y, double* out);
 
 #ifdef __cplusplus

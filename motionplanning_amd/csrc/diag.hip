@@ -5,7 +5,9 @@
 namespace {
 __global__ void math_kernel(int fn, long long n, const double* x, const double* y, double* out) {
   __shared__ double atab[20];
+  __shared__ double arows[4 * MPJ_ATAN_ROWS];
   if (threadIdx.x == 0) mpj_atan_tab_init(atab);
+  mpj_atan_rows_fill(arows, threadIdx.x, blockDim.x);
   __syncthreads();
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -37,19 +39,38 @@ __global__ void math_kernel(int fn, long long n, const double* x, const double* 
     case 21: { int b = 0; r = mpj_tan_wide(a, &b); r = b ? mpj_tan(a) : r; break; }
     case 22: r = mpj_sin_34(a); break;
     case 23: r = mpj_log_bl(a); break;
+    case 24: r = mpj_atan_rows(a, arows); break;
+    // exact cheap divisions a / y[i] (must equal `/`): guarded; hoisted reciprocal with the divisor checked
+    // by the caller; the same with the fixup taking zero, Inf and NaN numerators; the shared-reciprocal pair
+    case 25: r = mpj_div_g(a, y[i]); break;
+    case 26: r = mpj_div_gn(a, y[i], mpj_rcp_nr(y[i]), !mpj_div_out(y[i])); break;
+    case 27: r = mpj_div_gf(a, y[i], mpj_rcp_nr(y[i]), !mpj_div_out(y[i])); break;
+    case 28: { double q1, q2; mpj_div2_g(a, 1.0, y[i], &q1, &q2); r = q1; break; }
+    case 29: { double q1, q2; mpj_div2_g(-1.5, a, y[i], &q1, &q2); r = q2; break; }
+    // what v_div_scale_f64 does to a / y[i]: 1 numerator changed + 2 divisor changed + 4 VCC set (either call)
+    case 30: {
+      bool v0 = false, v1 = false;
+      const double dn = __builtin_amdgcn_div_scale(a, y[i], true, &v0);
+      const double dd = __builtin_amdgcn_div_scale(a, y[i], false, &v1);
+      const unsigned long long ua = (unsigned long long)__double_as_longlong(a), ud = (unsigned long long)__double_as_longlong(y[i]);
+      r = (double)(((unsigned long long)__double_as_longlong(dn) != ua ? 1 : 0) +
+                   ((unsigned long long)__double_as_longlong(dd) != ud ? 2 : 0) + ((v0 || v1) ? 4 : 0));
+      break;
+    }
   }
   out[i] = r;
 }
+bool two_op(int fn) { return fn == 4 || fn == 18 || fn >= 25; }
 }  // namespace
 
 extern "C" int mp_math_eval(mp_ctx* ctx, int32_t fn, int64_t n, const double* x, const double* y, double* out) {
   if (!ctx) return MP_ERR_INVALID;
-  MP_CHECK(ctx, fn >= 0 && fn <= 23 && n >= 0 && x && out && ((fn != 4 && fn != 18) || y), "bad mp_math_eval arguments");
+  MP_CHECK(ctx, fn >= 0 && fn <= 30 && n >= 0 && x && out && (!two_op(fn) || y), "bad mp_math_eval arguments");
   if (n == 0) return MP_OK;
   MP_HIP(ctx, hipSetDevice(ctx->device));
   int st = MP_OK;
   const double* dx = mp_upload(ctx, WS_IO0, x, (size_t)n, &st);
-  const double* dy = mp_upload(ctx, WS_IO1, (fn == 4 || fn == 18) ? y : nullptr, (size_t)n, &st);
+  const double* dy = mp_upload(ctx, WS_IO1, two_op(fn) ? y : nullptr, (size_t)n, &st);
   double* dout = mp_alloc_out(ctx, WS_IO2, out, (size_t)n, &st);
   if (st) return st;
   hipLaunchKernelGGL(math_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, fn, (long long)n, dx,

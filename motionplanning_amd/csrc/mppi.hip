@@ -34,8 +34,11 @@ constexpr int RPB = NT / 2; // rollouts per block
 #ifndef MPPI_PRIO
 #define MPPI_PRIO 3  // issue-priority scheme of the rollout loop (see ctrl()); 0 = quarters (round 2)
 #endif
-constexpr size_t kMaxLds = 148 * 1024;  // dynamic LDS budget per block (160 KiB per CU on gfx950)
-constexpr size_t kCoLds = 72 * 1024;    // budget that keeps two blocks co-resident per CU
+// Dynamic LDS budgets per block (160 KiB per CU on gfx950).  The plan kernel's static LDS is at most
+// 13,096 B (BT 512, LPR 2: sh_q 8 KiB, sh_e 2 KiB, the atan rows and bounds 2,704 B, the rest < 200 B), so one block
+// fits beside 146 KiB, and at most 7,976 B at BT 256, so two blocks fit beside 70 KiB each.
+constexpr size_t kMaxLds = 146 * 1024;
+constexpr size_t kCoLds = 70 * 1024;    // budget that keeps two blocks co-resident per CU
 
 __device__ __forceinline__ double block_reduce_min(double v, double* sh) {
   for (int o = 32; o >= 1; o >>= 1) v = nanmin(v, __shfl_xor(v, o));
@@ -202,7 +205,7 @@ __global__ __launch_bounds__(BT) void mppi_plan_kernel(MppiDev P, PlanArgs A) {
   __shared__ double sh_q[WPART ? NT / 64 : NQ][128];  // per-wave (WPART) or per-quarter control sums
   __shared__ int sh_last, sh_m, sh_bstar, sh_fc;
   __shared__ double sh_eta;
-  __shared__ double atab[20];  // mpj_atan_tab range constants
+  __shared__ double atab[kTabDoubles];  // rollout_tab_fill: atan range rows, state bounds
   extern __shared__ double dyn[];
   const int H = P.H, H2 = 2 * H, K = P.K;
   const int s = blockIdx.x / A.nb, b = blockIdx.x % A.nb;
@@ -230,7 +233,7 @@ __global__ __launch_bounds__(BT) void mppi_plan_kernel(MppiDev P, PlanArgs A) {
   const unsigned char* grid = nullptr;
   {
     const double* gu = A.unom + (size_t)H2 * s;
-    if (tid == 0) mpj_atan_tab_init(atab);
+    rollout_tab_fill(atab, P, tid, NT);
     for (int i = tid; i < H2; i += NT) unom[i] = gu[i];
     if (P.ctrl_cost)
       for (int i = tid; i < H; i += NT) ctrl_cost_row(P, gu[2 * i], gu[2 * i + 1], dyn + A.lds_cq + 2 * i);
@@ -650,14 +653,14 @@ __global__ __launch_bounds__(64) void final_rollout_kernel(MppiDev P, const doub
                                                            int grid_lds, double* traj_out, double* cost_out,
                                                            int* feas_out, int* flags) {
   extern __shared__ double fsh[];
-  __shared__ double atab[20];
+  __shared__ double atab[kTabDoubles];
   const int s = blockIdx.x, tid = threadIdx.x, side = tid & 1, H = P.H;
   const FinRec R(H, P.n_obs, P.gnx * P.gny);
   const double* rec = fin + (size_t)s * fin_stride;
   if (rec[R.ran] == 0.0) return;  // closed loop: the plan kernel of this call skipped the scene
   const int nw = grid_lds ? R.stride : R.grid;  // the grid stays in the record when it does not fit
   for (int i = tid; i < nw; i += 64) fsh[i] = rec[i];
-  if (tid == 0) mpj_atan_tab_init(atab);
+  rollout_tab_fill(atab, P, threadIdx.x, blockDim.x);
   __syncthreads();
   // issue priority 0 (lowest): the serial chain fills the issue bubbles of the next call's
   // rollout waves on its SIMD instead of delaying them (the plan kernel ends with its slowest
@@ -686,8 +689,8 @@ __global__ __launch_bounds__(NT) void rollout_kernel(MppiDev P, int K, const dou
   const int H = P.H;
   const int s = blockIdx.x / nb, b = blockIdx.x % nb;
   const int tid = threadIdx.x, pair = tid >> 1, side = tid & 1;
-  __shared__ double atab[20];
-  if (tid == 0) mpj_atan_tab_init(atab);
+  __shared__ double atab[kTabDoubles];
+  rollout_tab_fill(atab, P, threadIdx.x, blockDim.x);
   __syncthreads();
   const int k = b * RPB + pair;
   const bool active = k < K;
@@ -742,8 +745,8 @@ __global__ __launch_bounds__(64) void euler_kernel(int n, double* states, const 
   const int tid = blockIdx.x * 64 + threadIdx.x;
   const int v = tid >> 1, side = tid & 1;
   const int vv = v < n ? v : n - 1;
-  __shared__ double atab[20];
-  if (threadIdx.x == 0) mpj_atan_tab_init(atab);
+  __shared__ double atab[4 * MPJ_ATAN_ROWS];
+  mpj_atan_rows_fill(atab, threadIdx.x, blockDim.x);
   __syncthreads();
   double x[7], d[7];
   for (int i = 0; i < 7; i++) x[i] = states[7 * vv + i];
@@ -774,8 +777,8 @@ __global__ __launch_bounds__(64) void loop_plant_kernel(int S, int H, double* st
   const int tid = blockIdx.x * 64 + threadIdx.x;
   const int v = tid >> 1, side = tid & 1;
   const int vv = v < S ? v : S - 1;
-  __shared__ double atab[20];
-  if (threadIdx.x == 0) mpj_atan_tab_init(atab);
+  __shared__ double atab[4 * MPJ_ATAN_ROWS];
+  mpj_atan_rows_fill(atab, threadIdx.x, blockDim.x);
   __syncthreads();
   int* n_rows = st;
   int* live = st + S;

@@ -53,17 +53,17 @@ __device__ __forceinline__ double pair_swap(double v) {
 #define TY_SIN(x) ::sin(x)
 #define TY_SINCOS(a, s, c) ::sincos((a), (s), (c))
 #else
-#define TY_ATAN(x, tab) mpj_atan_tab((x), (tab))
+#define TY_ATAN(x, tab) mpj_atan_rows((x), (tab))
 #define TY_SIN(x) mpj_sin_34(x)
 #define TY_SINCOS(a, s, c) mpj_sincos_bl((a), (s), (c))
 #endif
 // VehicleDynamics for a lane pair.  side = lane & 1 (0: front tire, 1: rear).
-// atab: the mpj_atan_tab range table (LDS).
+// atab: the mpj_atan_rows range table (LDS, 4 * MPJ_ATAN_ROWS doubles; rollout_pair: the whole rollout_tab_fill block).
 //
 // Lane constants of the pair, fixed for a rollout (kept in registers instead of selected every
 // call): the axle load constant, the sign of t, the slip lever arm, the force-division operands.
 struct PairK {
-  double kfz, tsg, lr, cown, cother, div;
+  double kfz, tsg, lr, cown, cother, div, rdiv;  // rdiv = mpj_rcp_nr(div): the divisor never changes
 };
 __device__ __forceinline__ PairK pair_k(int side) {
   const double la = 1.56, lb = 1.64, M = 2020.0, Izz = 4095.0;
@@ -75,6 +75,7 @@ __device__ __forceinline__ PairK pair_k(int side) {
   k.cown = side ? -lb : 1.0;
   k.cother = side ? la : 1.0;
   k.div = side ? Izz : M;
+  k.rdiv = mpj_rcp_nr(k.div);
   return k;
 }
 // dyn_pair with sin/cos(ψ) supplied (rollout_pair evaluates both RK2 stages' in one call)
@@ -87,7 +88,8 @@ __device__ __forceinline__ void dyn_pair_sc(const double* x, double sr, double a
   // front: 2*(KFZF*g - t);  rear: 2*(KFZR*g + t)   (vehicledynamics.jl:30-31); t·(∓1) is exact
   const double FZ = 2 * (pk.kfz * g + t * pk.tsg);
   // front: (v + la*r) ... - sa;  rear: (v - lb*r) ... [(-lb)*r == -(lb*r) exactly]  (:32-33)
-  const double alpha = TY_ATAN((v + pk.lr * r) / (ux + 0.01), atab) - (side ? 0.0 : sa);
+  // ux + 0.01 can be zero, tiny or huge and the numerator zero: guarded (mpj_div_g), plain `/` then
+  const double alpha = TY_ATAN(mpj_div_g(v + pk.lr * r, ux + 0.01), atab) - (side ? 0.0 : sa);
   const double X1 = B * alpha;
   const double FY = mu * FZ * 1.0 * TY_SIN(C * TY_ATAN(X1 - E * (X1 - TY_ATAN(X1, atab)), atab));  // (:35-38)
   const double FYo = pair_swap(FY);
@@ -98,7 +100,9 @@ __device__ __forceinline__ void dyn_pair_sc(const double* x, double sr, double a
   // (FY1*la - FY2*lb)/Izz, exchanged with one DPP swap.  The numerator is own·cown + other·cother:
   // the same two rounded products (x·1.0 = x, y·(-lb) = -(y·lb)) summed commutatively, so the
   // same bits as the reference expression without selecting FY1/FY2 per lane.
-  const double q = (FY * pk.cown + FYo * pk.cother) / pk.div;
+  // pk.div is 2020 or 4095, inside the no-scaling window; the numerator (0 when the slip angles are,
+  // unbounded when the state diverges) is guarded
+  const double q = mpj_div_gn(FY * pk.cown + FYo * pk.cother, pk.div, pk.rdiv, 1);
   const double qo = pair_swap(q);
   d[2] = (side ? qo : q) - r * uxc;
   d[3] = side ? q : qo;
@@ -117,15 +121,30 @@ __device__ __forceinline__ void dyn_pair(const double* x, double sr, double ax, 
 // the same operands, so the same bits), no lane exchange.  Used when the launch has enough
 // rollouts for one per lane to fill every SIMD: the costs and the state update are then not
 // evaluated twice, and the two tire chains interleave in the single wave's latency bubbles.
-__device__ __forceinline__ void dyn_lane(const double* x, double sr, double ax, double* d, const double* atab) {
+// rM, rI: mpj_rcp_nr(M), mpj_rcp_nr(Izz), evaluated once per rollout.
+struct LaneK {
+  double rM, rI;
+};
+__device__ __forceinline__ LaneK lane_k() {
+  LaneK k;
+  k.rM = mpj_rcp_nr(2020.0);
+  k.rI = mpj_rcp_nr(4095.0);
+  return k;
+}
+__device__ __forceinline__ void dyn_lane(const double* x, double sr, double ax, double* d, const double* atab,
+                                         const LaneK& lk) {
   const double la = 1.56, lb = 1.64, M = 2020.0, Izz = 4095.0, g = 9.81, mu = 0.8;
   const double KFZF = 1018.28 / 2, KFZR = 963.34 / 2, KFZX = 186.22;
   const double B = -10.4 / mu, C = 1.3, E = 0.1556;
   const double v = x[2], r = x[3], psi = x[4], ux = x[5], sa = x[6];
   const double t = (ax - r * v) * KFZX;
   const double FZf = 2 * (KFZF * g + -t), FZr = 2 * (KFZR * g + t);
-  const double af = TY_ATAN((v + la * r) / (ux + 0.01), atab) - sa;
-  const double ar = TY_ATAN((v + (-lb) * r) / (ux + 0.01), atab) - 0.0;
+  // the two slip-angle quotients share the divisor ux + 0.01, which can be zero, tiny or huge, and
+  // either numerator can be zero: one guard over the three operands, one reciprocal (mpj_div2_g)
+  double qf, qr;
+  mpj_div2_g(v + la * r, v + (-lb) * r, ux + 0.01, &qf, &qr);
+  const double af = TY_ATAN(qf, atab) - sa;
+  const double ar = TY_ATAN(qr, atab) - 0.0;
   const double Xf = B * af, Xr = B * ar;
   const double FY1 = mu * FZf * 1.0 * TY_SIN(C * TY_ATAN(Xf - E * (Xf - TY_ATAN(Xf, atab)), atab));
   const double FY2 = mu * FZr * 1.0 * TY_SIN(C * TY_ATAN(Xr - E * (Xr - TY_ATAN(Xr, atab)), atab));
@@ -134,8 +153,10 @@ __device__ __forceinline__ void dyn_lane(const double* x, double sr, double ax, 
   TY_SINCOS(psi, &sp, &cp);
   d[0] = uxc * cp - v * sp;
   d[1] = uxc * sp + v * cp;
-  d[2] = (FY1 + FY2) / M - r * uxc;
-  d[3] = (FY1 * la - FY2 * lb) / Izz;
+  // M and Izz are inside the no-scaling window; the numerators (0 when the slip angles are, unbounded
+  // when the state diverges) are guarded
+  d[2] = mpj_div_gn(FY1 + FY2, M, lk.rM, 1) - r * uxc;
+  d[3] = mpj_div_gn(FY1 * la - FY2 * lb, Izz, lk.rI, 1);
   d[4] = r;
   d[5] = ax;
   d[6] = sr;
@@ -149,9 +170,24 @@ __device__ __forceinline__ double run_cost(const double* x, double sr, double ax
 
 // ObstacleEvaluation (MPPIUtils.jl:120-132) + occupancy grid (build extension).
 // Branch-free: `c = hit ? c + pen : c` is bit-identical to `if (hit) c = c + pen`.
+// The cell-size reciprocals of the occupancy grid (launch constants), evaluated once per rollout:
+// rx, ry = mpj_rcp_nr(gdx), mpj_rcp_nr(gdy) (LPR 2: rx holds the lane's own, even gdx, odd gdy);
+// ok: both cell sizes are inside the no-scaling window (wave-uniform), else the divisions stay plain.
+struct GridK {
+  double rx, ry;
+  int ok;
+};
+template <int LPR = 2>
+__device__ __forceinline__ GridK grid_k(const MppiDev& P, int side) {
+  GridK g;
+  g.rx = mpj_rcp_nr(LPR == 2 && side ? P.gdy : P.gdx);
+  g.ry = mpj_rcp_nr(P.gdy);
+  g.ok = P.gnx > 0 && !mpj_div_out(P.gdx) && !mpj_div_out(P.gdy);
+  return g;
+}
 template <int LPR = 2>
 __device__ __forceinline__ double obstacle_cost(const MppiDev& P, const double* x, const double* obs,
-                                                const unsigned char* grid, int* ok, int side) {
+                                                const unsigned char* grid, int* ok, int side, const GridK& gk) {
   double c = 0.0;
   for (int o = 0; o < P.n_obs; o++) {
     const double dx = x[0] - obs[3 * o], dy = x[1] - obs[3 * o + 1], R = obs[3 * o + 2];
@@ -162,13 +198,14 @@ __device__ __forceinline__ double obstacle_cost(const MppiDev& P, const double* 
   if (P.gnx > 0) {
     double fx, fy;
     if (LPR == 2) {  // cell coordinates: even lane divides x, odd lane y, one DPP swap
-      const double f = (side ? x[1] - P.gy0 : x[0] - P.gx0) / (side ? P.gdy : P.gdx);
+      const double f = mpj_div_gn(side ? x[1] - P.gy0 : x[0] - P.gx0, side ? P.gdy : P.gdx, gk.rx, gk.ok);
       const double fo = pair_swap(f);
       fx = side ? fo : f;
       fy = side ? f : fo;
     } else {
-      fx = (x[0] - P.gx0) / P.gdx;
-      fy = (x[1] - P.gy0) / P.gdy;
+      // the numerators (0 on a grid line through the origin, unbounded when the state diverges) are guarded
+      fx = mpj_div_gn(x[0] - P.gx0, P.gdx, gk.rx, gk.ok);
+      fy = mpj_div_gn(x[1] - P.gy0, P.gdy, gk.ry, gk.ok);
     }
     const int inb = fx >= 0.0 && fy >= 0.0 && fx < (double)P.gnx && fy < (double)P.gny;
     const int ix = inb ? (int)fx : 0, iy = inb ? (int)fy : 0;
@@ -179,20 +216,40 @@ __device__ __forceinline__ double obstacle_cost(const MppiDev& P, const double* 
   return c;
 }
 
-// BoundEvaluation, MPPIUtils.jl:135-151 (branch-free, same accumulation order)
-__device__ __forceinline__ double bound_cost(const MppiDev& P, const double* x, int* ok) {
+// The rollout's uniform LDS block (`atab` of rollout_pair): the mpj_atan_rows range rows, then the state
+// bounds {XL[i], XU[i]}, i = 0..6.  The bounds are read from LDS once per step instead of holding 28
+// scalar registers across the rollout loop, which the loop does not have: the allocator kept them, and
+// what they displaced, in VGPR lanes and fetched them back with v_readlane (VALU issue) every step.
+constexpr int kTabBnd = 4 * MPJ_ATAN_ROWS, kTabDoubles = kTabBnd + 14;
+__device__ __forceinline__ void rollout_tab_fill(double* tab, const MppiDev& P, unsigned tid, unsigned step) {
+  mpj_atan_rows_fill(tab, tid, step);
+  if (tid == 0) {
+#pragma unroll
+    for (int i = 0; i < 7; i++) {
+      tab[kTabBnd + 2 * i] = P.XL[i];
+      tab[kTabBnd + 2 * i + 1] = P.XU[i];
+    }
+  }
+}
+
+// BoundEvaluation, MPPIUtils.jl:135-151 (branch-free, same accumulation order); bnd = tab + kTabBnd
+__device__ __forceinline__ double bound_cost(const MppiDev& P, const double* bnd, const double* x, int* ok) {
+  // an opaque copy of the address: the 14 loads stay inside the step (hoisted out of the rollout loop they
+  // would hold 28 VGPRs across it)
+  asm volatile("" : "+v"(bnd));
   int viol = 0;
 #pragma unroll
-  for (int i = 0; i < 7; i++) viol |= (x[i] < P.XL[i]) | (x[i] > P.XU[i]);
+  for (int i = 0; i < 7; i++) viol |= (x[i] < bnd[2 * i]) | (x[i] > bnd[2 * i + 1]);
   *ok &= !viol;
   double c = 0.0;
   if (__any(viol)) {  // wave-uniform: with no violation in the wave every lane's sum is exactly 0.0
 #pragma unroll
     for (int i = 0; i < 7; i++) {
-      const int lo = x[i] < P.XL[i], hi = x[i] > P.XU[i];
-      const double vl = c + P.slack * __builtin_fabs(x[i] - P.XL[i]);
+      const double xl = bnd[2 * i], xu = bnd[2 * i + 1];
+      const int lo = x[i] < xl, hi = x[i] > xu;
+      const double vl = c + P.slack * __builtin_fabs(x[i] - xl);
       c = lo ? vl : c;
-      const double vh = c + P.slack * __builtin_fabs(x[i] - P.XU[i]);
+      const double vh = c + P.slack * __builtin_fabs(x[i] - xu);
       c = hi ? vh : c;
     }
   }
@@ -329,6 +386,8 @@ __device__ __forceinline__ double rollout_pair(const MppiDev& P, const double* X
 #pragma unroll
   for (int i = 0; i < 7; i++) x[i] = X0[i];
   const PairK pk = pair_k(side);
+  const LaneK lk = lane_k();
+  const GridK gk = grid_k<LPR>(P, side);
   if (traj.p) store_state<LPR>(traj, 0, x, side);
   double sum = 0.0;
   int ok_all = 1;
@@ -339,8 +398,8 @@ __device__ __forceinline__ double rollout_pair(const MppiDev& P, const double* X
     int okc = 1, okb = 1;
     double cc = 0.0, cb = 0.0;
     if (j > 0) {
-      cc = obstacle_cost<LPR>(P, x, obs, grid, &okc, side);
-      cb = bound_cost(P, x, &okb);
+      cc = obstacle_cost<LPR>(P, x, obs, grid, &okc, side, gk);
+      cb = bound_cost(P, atab + kTabBnd, x, &okb);
     }
     const double pc = run_cost(x, u[0], u[1]);
     double k1[7], k2[7], x2[7];
@@ -357,10 +416,10 @@ __device__ __forceinline__ double rollout_pair(const MppiDev& P, const double* X
       for (int i = 0; i < 7; i++) x2[i] = x[i] + k1[i] * P.dt;
       dyn_pair_sc(x2, u[0], u[1], k2, side, atab, side ? sn : so, side ? cs : co, pk);
     } else {
-      dyn_lane(x, u[0], u[1], k1, atab);
+      dyn_lane(x, u[0], u[1], k1, atab, lk);
 #pragma unroll
       for (int i = 0; i < 7; i++) x2[i] = x[i] + k1[i] * P.dt;
-      dyn_lane(x2, u[0], u[1], k2, atab);
+      dyn_lane(x2, u[0], u[1], k2, atab, lk);
     }
 #pragma unroll
     for (int i = 0; i < 7; i++) x[i] = x[i] + P.dt * (k1[i] + k2[i]) / 2;
@@ -384,8 +443,8 @@ __device__ __forceinline__ double rollout_pair(const MppiDev& P, const double* X
   {  // terminal (:49-54): only the running cost of the extra RK2 step is used
     int okc = 1, okb = 1;
     const double pc = run_cost(x, 0.0, 0.0);
-    const double cc = obstacle_cost<LPR>(P, x, obs, grid, &okc, side);
-    const double cb = bound_cost(P, x, &okb);
+    const double cc = obstacle_cost<LPR>(P, x, obs, grid, &okc, side, gk);
+    const double cb = bound_cost(P, atab + kTabBnd, x, &okb);
     sum = sum + (pc + cb + cc);
     ok_all &= okc & okb;
   }
