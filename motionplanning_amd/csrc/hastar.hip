@@ -10,8 +10,9 @@
 //                     on 16 lanes, the (neighbour, pose) SAT collision sweep across all
 //                     lanes, then the 48-candidate rs_heuristic of all 16 neighbours at once
 //                     (lanes 4j..4j+3 = the four variants of neighbour j, word loop uniform).
-// ha_book_kernel: the open list / Dict bookkeeping of planHybridAstar! and the next pop, on the
-// device (mp_ha_plan enqueues the whole search without host round trips).
+// ha_step_kernel / ha_pipe_kernel / ha_persist_kernel: the same block roles plus the open list / Dict
+// bookkeeping of planHybridAstar! and the next pop, on the device (mp_ha_plan enqueues the whole search
+// without host round trips; the shapes and their hand-overs are described at each kernel).
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -41,20 +42,9 @@ __device__ int* g_ha_dbg;
     if (threadIdx.x == 0)                                                                          \
       reinterpret_cast<unsigned long long*>(g_ha_dbg + 64 * 64)[blockIdx.x * 16 + (i)] = __builtin_amdgcn_s_memtime(); \
   } while (0)
-// bookkeeping-kernel stamps of scene b at [b][16] after the iteration kernel's 4096 blocks, at
-// iteration HA_DBG_IT
-#ifndef HA_DBG_IT
-#define HA_DBG_IT 20
-#endif
-#define BTIME(i)                                                                                   \
-  do {                                                                                             \
-    if (threadIdx.x == 0 && it == HA_DBG_IT)                                                       \
-      reinterpret_cast<unsigned long long*>(g_ha_dbg + 64 * 64)[(4096 + b) * 16 + (i)] = __builtin_amdgcn_s_memtime(); \
-  } while (0)
 #else
 #define HMARK(ph)
 #define HTIME(i)
-#define BTIME(i)
 #endif
 
 struct HaDev {
@@ -124,17 +114,7 @@ __constant__ signed char kRsTr[12][5] = {{0, 1, 2}, {0, 1, 2}, {0, 1, 2}, {0, 1,
                                          {0, 3, 1, 2}, {0, 1, 3, 2}, {0, 3, 1, 3, 2}};
 __constant__ signed char kRsN[12] = {3, 3, 3, 3, 3, 4, 4, 4, 4, 4, 4, 5};
 
-// (A/B) HA_RS_NOINLINE=1: one out-of-line copy of rs_word instead of one per call site (the step
-// kernel's instruction footprint)
-#ifndef HA_RS_NOINLINE
-#define HA_RS_NOINLINE 0
-#endif
-#if HA_RS_NOINLINE
-#define RS_WORD_ATTR __attribute__((noinline))
-#else
-#define RS_WORD_ATTR __forceinline__
-#endif
-__device__ RS_WORD_ATTR double rs_word(int w_, const RsPre& R, Cmd* c, double* tuv = nullptr) {
+__device__ __forceinline__ double rs_word(int w_, const RsPre& R, Cmd* c, double* tuv = nullptr) {
   const int w = __builtin_amdgcn_readfirstlane(w_);  // wave-uniform word: scalar branches and table loads
   const double p = R.p;
   const bool useA = (w == 1) | (w == 3) | (w == 4) | (w == 5) | (w == 8) | (w == 9);
@@ -597,7 +577,7 @@ struct IterArgs {
   long long* idx;        // [B][n_prim]
   unsigned char* fr;     // [B][n_prim]
   double* h;             // [B][n_prim]
-  // (mp_ha_plan, HA_RS_WINNER) rs_heuristic's winning Reeds-Shepp candidate (0..47) per neighbour, -1 when
+  // (mp_ha_plan) rs_heuristic's winning Reeds-Shepp candidate (0..47) per neighbour, -1 when
   // the group did not evaluate it; and the popped node's stored winner per scene (-1: unknown -> RS_connected
   // runs the full 48-candidate search).  A node's states never change after its creation (FindNewNode's
   // update branch, hybrid_astar_utils.jl:425-430, touches g/h/f/parent only), and RS_connected (:229-230)
@@ -621,34 +601,21 @@ struct IterArgs {
   // transform / regulate_states / Encode (:396-405), nullptr = compute
   const double* htn;
   const double* htk;
-  int no_pre;  // (A/B, MPGPU_HA_PRESCAN=0) the prescan block only marks its record stale: the bookkeeping scans
-  int rs_last;  // ha_step_kernel dispatches the RS_connected blocks last ((A/B) MPGPU_HA_RS_LAST=0: first)
+  // the flags below (no_pre, rs_last, ngr_pub, no_tuv) and `mirror` are constants of mp_ha_plan today: true, true,
+  // true, false and nullptr
+  int no_pre;   // the prescan block only marks its record stale: the bookkeeping scans
+  int rs_last;  // ha_step_kernel dispatches the RS_connected blocks last
   int node_ag;  // read the node agent-coherently (written in this launch), once node_flag[s] >= node_flag_min
   // (tail pipe / persistent launches) the node as tagged granules instead: [B][HA_NGR] of {tag, 32-bit value},
   // this parity's, complete once every tag equals ngr_tag (see ha_publish_node)
   const unsigned long long* ngr;
   unsigned ngr_tag;
-  int ngr_pub;  // the tail's bookkeeping publishes granules (else the node buffers + a drained flag); (A/B) MPGPU_HA_NGR
+  int ngr_pub;  // the tail's bookkeeping publishes granules (else the node buffers + a drained flag)
   const int* node_flag;
   int node_flag_min;
   int* node_flag_err;  // the wait is bounded: past HA_SPIN_MAX polls it sets *node_flag_err and gives up
-  // (full-width ha_pipe_kernel) the popped node's g and the scene's node count before its FindNewNode, published
-  // with the node: the Dict pre-check then runs beside FindNewNode's writes (see ha_iter_body)
-  const double* node_g;
-  const int* node_nn;
-  int full_tuv;  // the full-width groups store their winners' (t, u, v) (hp_t chunk 0) and the books flag them
   unsigned long long* mirror;  // (host-coherent) launch it's first block writes (it - 1) << 32 | live(it - 1)
-  // [B][n_prim][HA_DREC] (full-width / middle step launches) each neighbour's Dict entry as the group found it:
-  // cell's node id, then its g, pos, f, seq, Encode index, rs winner, state -- the bookkeeping reads them with
-  // the other records instead of looking them up after them
-  long long* drec;
-  const int* dpos;
-  const double* df;
-  const long long* dseq;
-  const long long* dindex;
-  const int* drw;
-  const double* dst;
-  int no_tuv;  // (A/B, MPGPU_HA_TUV=0) nodes keep only their winner id: RS_connected evaluates its word
+  int no_tuv; // nodes keep only their winner id: RS_connected evaluates its word
 };
 
 // Agent-coherent relaxed stores / loads (global_store / global_load with the sc1 policy: they reach
@@ -711,14 +678,6 @@ __device__ __forceinline__ void ha_mirror(const IterArgs& A, int it) {
     __hip_atomic_store(A.mirror, ((unsigned long long)(it - 1) << 32) | (unsigned)*A.n_live, __ATOMIC_RELAXED,
                        __HIP_MEMORY_SCOPE_SYSTEM);
 }
-
-constexpr int HA_DREC = 10;
-// (A/B build -DHA_DREC_CODE=1 + MPGPU_HA_DREC=1) the step launches' groups copy their neighbours' Dict entries
-// into the records: bit-exact but 0.3-0.5 ms slower per 256-plan (r05zf: the groups' extra loads / stores and
-// registers cost more than the bookkeeping's saved round trip), so compiled out by default
-#ifndef HA_DREC_CODE
-#define HA_DREC_CODE 0
-#endif
 
 // Bounded cross-block wait (ha_pipe_kernel, ha_persist_kernel): poll *p until it is >= v; past HA_SPIN_MAX
 // polls (~1 s) set *err and return HA_DONE (every waiter then leaves its loop: a wrong result, not a hang)
@@ -838,44 +797,26 @@ static_assert(12 % HW == 0, "HA_WAVES must divide the 12 Reeds-Shepp words");
 #define HA_NBG_TAIL 4
 #endif
 constexpr int HW_TAIL = 12, NBG_TAIL = HA_NBG_TAIL;
-// the middle shape's waves per block (MPGPU_HA_MID_BLOCKS): 16 neighbours each, 12 / HA_MID_HW Reeds-Shepp
+// the middle shape's waves per block (HA_MID_BLOCKS): 16 neighbours each, 12 / HA_MID_HW Reeds-Shepp
 // words per wave (12-wave blocks measured 38 ms per 256-plan at MID 1024, r05q; 6-wave ones 24.9, r05x)
 #ifndef HA_MID_HW
 #define HA_MID_HW 6
 #endif
-// (A/B) -DHA_TAIL_OVERLAP=1: the tail shape's neighbour groups evaluate rs_heuristic for all their
-// neighbours, overlapped with the sweep, instead of sweeping first and evaluating it only when a neighbour
-// needs it (as the full-width shape does).  Measured slower (r05e, lone 729-pop scenario: 29.1 vs 28.3 us
-// per iteration): with 4 neighbours per group a word fills 16 of a wave's 64 lanes, and the group's 12
-// waves (3 per SIMD) are issue-bound -- the word search takes ~10 us on every group instead of ~8.5 us on
-// the groups that need it.
+// the tail shape's rs_heuristic in word units spread over the scene's groups (ha_iter_body RSH); 0, or a
+// primitive count that does not tile: the groups' own word search after their sweep.  (The groups' own search
+// for all their neighbours overlapped with the sweep measured slower on the lone 729-pop scenario, 29.1 vs
+// 28.3 us per iteration, profiles/r05e_ha_lone_block_stamps_overlap.txt.)
 #ifndef HA_TAIL_RSH
 #define HA_TAIL_RSH 1
-#endif
-// (A/B build, -DHA_FULL_TUV_CODE=1 + MPGPU_HA_FULL_TUV=1) the full-width groups' winners' (t, u, v) carried
-// through the full-width bookkeeping too (see the host's ftuv_env)
-#ifndef HA_FULL_TUV_CODE
-#define HA_FULL_TUV_CODE 0
-#endif
-#ifndef HA_TAIL_OVERLAP
-#define HA_TAIL_OVERLAP 0
 #endif
 
 // allpath + findmin split over the block's HW waves: wave w evaluates words WPW·w+1..WPW·(w+1) for
 // its lanes' candidates (lane&3 = variant of the state in `s`), the per-wave winners are
 // combined in LDS in word order with the same total order (rs_before).  Every wave returns
 // the block-wide winner for its lanes; *best_id is the winning candidate id.
-struct NoMid {
-  __device__ void operator()() const {}
-};
-// mid(): work the block does between its word loop and the cross-wave reduction (the tail shape's collision
-// sweep), so the waves' Reeds-Shepp chains and that work overlap on the SIMDs instead of following each other
-// TUV (the full-width groups): every lane also keeps its best word's (t, u, v) through the word loop and the
-// variant reduction, into tv_out; the lanes of wave (id / 4) / WPW then hold the block winner's
-template <bool CMD, int HWt, class Mid = NoMid, bool TUV = false>
+template <bool CMD, int HWt>
 __device__ __forceinline__ double rs_best_split(const double* s, int tid, int* best_id, double* sh_c, int* sh_i,
-                                                double* cmd_out = nullptr, const Mid& mid = Mid(),
-                                                double* tv_out = nullptr) {
+                                                double* cmd_out = nullptr) {
   constexpr int WPW = 12 / HWt;  // Reeds–Shepp words per wave
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, var = lane & 3;
   double q[3];
@@ -889,43 +830,27 @@ __device__ __forceinline__ double rs_best_split(const double* s, int tid, int* b
   // register peak, so the winning word is evaluated again below
   constexpr bool KEEP = CMD && WPW == 1;
   Cmd cb;
-  double tb[3] = {0.0, 0.0, 0.0};
 #pragma unroll 1
   for (int w = WPW * wave + 1; w <= WPW * wave + WPW; w++) {
-    double tw[3];
-    const double cost = rs_word(w, R, KEEP ? &cb : nullptr, TUV ? tw : nullptr);
+    const double cost = rs_word(w, R, KEEP ? &cb : nullptr);
     const int id = 4 * (w - 1) + var;
     if (rs_before(cost, id, bc, bi)) {
       bc = cost;
       bi = id;
-      if (TUV)
-#pragma unroll
-        for (int e = 0; e < 3; e++) tb[e] = tw[e];
     }
   }
 #pragma unroll
   for (int o = 2; o >= 1; o >>= 1) {
     const double ov = __shfl_xor(bc, o);
     const int oi = __shfl_xor(bi, o);
-    double ot[3];
-    if (TUV)
-#pragma unroll
-      for (int e = 0; e < 3; e++) ot[e] = __shfl_xor(tb[e], o);
     if (rs_before(ov, oi, bc, bi)) {
       bc = ov;
       bi = oi;
-      if (TUV)
-#pragma unroll
-        for (int e = 0; e < 3; e++) tb[e] = ot[e];
     }
   }
-  if (TUV)
-#pragma unroll
-    for (int e = 0; e < 3; e++) tv_out[e] = tb[e];
   HTIME(13);
   sh_c[tid] = bc;
   sh_i[tid] = bi;
-  mid();
   __syncthreads();
   double v = sh_c[lane];
   int ix = sh_i[lane];
@@ -1061,8 +986,8 @@ __device__ __forceinline__ bool ha_iter_body(const HaDev& P, const IterArgs& A, 
   const int nw = P.n_walls;
   const double* node = A.node + 3 * s;
   const double* goal = A.goal + 3 * s;
-  __shared__ double nd_s[3], nd_g, nd_tuv[3];
-  __shared__ int nd_go, nd_nn, nd_rw;
+  __shared__ double nd_s[3], nd_tuv[3];
+  __shared__ int nd_go, nd_rw;
   const OutRef R = out_ref(A, s, P.n_prim);
   const int k0 = rs ? 0 : (item - 1) * NBG, nk = rs ? 0 : min(NBG, P.n_prim - k0);
   // wall corners (Block2Pts) and their SAT tables in LDS: precomputed once per plan
@@ -1104,8 +1029,6 @@ __device__ __forceinline__ bool ha_iter_body(const HaDev& P, const IterArgs& A, 
       __syncthreads();
       if (!nd_go) return false;  // block-uniform: the search ended, nothing to expand
       if (tid < 3) nd_s[tid] = ld_ag(A.node + 3 * s + tid);
-      if (tid == 3 && A.node_g) nd_g = ld_ag(A.node_g + s);
-      if (tid == 4 && A.node_g) nd_nn = ld_ag(A.node_nn + s);
       __syncthreads();
     }
     node = nd_s;
@@ -1123,7 +1046,7 @@ __device__ __forceinline__ bool ha_iter_body(const HaDev& P, const IterArgs& A, 
     const long long ix = expand_nb(P, A, node, tabm, k, nb, &sn, &cn);
     g_sc[tid][0] = sn;
     g_sc[tid][1] = cn;
-    if (!rs && !RSH && !(SPLIT && HA_TAIL_OVERLAP) && A.dnid) hit = ix > 0 && ix < A.C ? A.dnid[(size_t)s * A.C + ix] : -1;
+    if (!rs && !RSH && A.dnid) hit = ix > 0 && ix < A.C ? A.dnid[(size_t)s * A.C + ix] : -1;
     st_out(A.coherent, R.nb + 3 * k, nb[0]);
     st_out(A.coherent, R.nb + 3 * k + 1, nb[1]);
     st_out(A.coherent, R.nb + 3 * k + 2, nb[2]);
@@ -1138,13 +1061,8 @@ __device__ __forceinline__ bool ha_iter_body(const HaDev& P, const IterArgs& A, 
   HSTAMP(12);
   __syncthreads();
   const int j = lane >> 2;
-  // (A/B build -DHA_SWEEP_PROBE=1, non-RSH groups) the last swept pose of every neighbour first: a neighbour that
-  // collides there (the far end of its primitive) skips its other poses -- whole waves of them, as a wave covers
-  // about one neighbour's poses.  Same result (an OR over poses); measured 0.3-0.4 ms slower per 256-plan
-  // (r05zt: the extra phase and barrier cost more than the skipped rounds), so off.
-#ifndef HA_SWEEP_PROBE
-#define HA_SWEEP_PROBE 0
-#endif
+  // (Sweeping every neighbour's last pose first, so that one colliding there skips its other poses, measured
+  // 0.3-0.4 ms slower per 256-plan, profiles/r05zt_ha_sweep_probe_ab.txt.)
   auto sweep = [&](int npose, int nthr = 64 * HWt) {
     double nsn = 0.0, ncs = 1.0;
     if (!rs) {
@@ -1178,19 +1096,12 @@ __device__ __forceinline__ bool ha_iter_body(const HaDev& P, const IterArgs& A, 
       }
       if (!fr) g_free[jn] = 0;  // every writer stores 0
     };
-    constexpr bool PROBE = HA_SWEEP_PROBE && !RSH && !SPLIT;
-    if (PROBE && !rs && npose > 1) {  // block-uniform
-      for (int t = tid; t < nk; t += nthr)
-        if (g_ix[t] != 0 && g_free[t]) item(t, npose - 1, 0);
-      __syncthreads();
-    }
     const int total = (rs ? npose : nk * npose) * parts;
     for (int t = tid; t < total; t += nthr) {
       const int tp = SPLIT ? t / parts : t, part = SPLIT ? t - tp * parts : 0;
       const int jn = rs ? 0 : tp / npose, jp = rs ? tp : tp - jn * npose;
       if (!rs && g_ix[jn] == 0) continue;  // Encode 0: skipped before the collision check (:406-408)
       if (!g_free[jn]) continue;  // already colliding: block_collision_check stops at its first hit
-      if (PROBE && !rs && npose > 1 && jp == npose - 1) continue;  // (probed above)
       item(jn, jp, part);
     }
   };
@@ -1391,61 +1302,22 @@ __device__ __forceinline__ bool ha_iter_body(const HaDev& P, const IterArgs& A, 
     }
     HSTAMP(14);
     HSTAMP(15);
-  } else if (SPLIT && HA_TAIL_OVERLAP) {
-    // tail shape (latency-bound: CUs to spare, one scene's chain): rs_heuristic of every neighbour of the
-    // group, whether or not FindNewNode will read it, without waiting for the collision sweep; the sweep
-    // runs between each wave's Reeds-Shepp word and the cross-wave reduction, so the two overlap
-    double ns[3];
-    const int jj = j < nk ? j : 0;
-    change_basis_sc(g_nb[jj], goal, P.minR, g_sc[jj][0], g_sc[jj][1], ns);
-    const int npose = P.n_col > 5 ? (P.n_col - 1) / 5 + 1 : 1;
-    cb = rs_best_split<false, HWt>(ns, tid, &best, red_c, red_i, nullptr, [&] { sweep(npose); });
-    HSTAMP(13);
-    HSTAMP(14);
-    HSTAMP(15);
   } else {
     // dg_cost first (primitive poses 1:5:n_col): rs_heuristic is only used for neighbours that
     // are collision-free and in bounds, so a group without one skips the 48 RS candidates.
     // FindNewNode (:418-446) also leaves a neighbour alone whose cell already holds a node with
     // g <= tg = g(popped) + expand_time (the same tg for every neighbour): its heuristic is never read.
     // The Dict at this launch is the one this iteration's FindNewNode starts from (the bookkeeping
-    // that changes it runs after every neighbour group of the scene, ha_step_kernel / ha_book_kernel).
+    // that changes it runs after every neighbour group of the scene, ha_step_kernel).
+    // (The groups also copying the rest of their neighbours' Dict entries into the records, to save the
+    // bookkeeping's round trip, measured 0.3-0.5 ms slower per 256-plan, profiles/r05zf_ha_drec_ab.txt.)
     double gd = 0.0;
-    if (hit >= 0) gd = A.dg[(size_t)s * A.C + hit];  // loaded now, used after the sweep (a node newer than
-    // the pipelined launch's nn_lim below may be half-written: its g is loaded but never used)
-    // (step launches) the rest of the neighbour's Dict entry for the bookkeeping, loaded beside gd and stored
-    // after the sweep (the Dict is the one this iteration's FindNewNode starts from: it runs after every group)
-    const bool drec = HA_DREC_CODE && A.drec && A.dnid && !A.node_ag && tid < nk;
-    long long dv[HA_DREC - 2];
-    if (drec && hit >= 0) {
-      const size_t q = (size_t)s * A.C + hit;
-      dv[0] = A.dpos[q];
-      dv[1] = __double_as_longlong(A.df[q]);
-      dv[2] = A.dseq[q];
-      dv[3] = A.dindex[q];
-      dv[4] = A.drw[q];
-#pragma unroll
-      for (int e = 0; e < 3; e++) dv[5 + e] = __double_as_longlong(A.dst[q * 3 + e]);
-    }
+    if (hit >= 0) gd = A.dg[(size_t)s * A.C + hit];  // loaded now, used after the sweep
     sweep(P.n_col > 5 ? (P.n_col - 1) / 5 + 1 : 1);
-    if (drec) {
-      long long* o = A.drec + ((size_t)s * P.n_prim + k0 + tid) * HA_DREC;
-      st_out(A.coherent, o, (long long)hit);
-      if (hit >= 0) {
-        st_out(A.coherent, o + 1, __double_as_longlong(gd));
-#pragma unroll
-        for (int e = 0; e < HA_DREC - 2; e++) st_out(A.coherent, o + 2 + e, dv[e]);
-      }
-    }
     HTIME(4);
     HSTAMP(13);
-    // (full-width ha_pipe_kernel) this iteration's FindNewNode writes the Dict meanwhile: only nodes older than
-    // it (id < its starting node count) are trusted, and their g only decreases, so the g read (the old or the
-    // new value) >= the g FindNewNode(n_{it+1}) compares with: a skip stays a skip
-    const bool pub = A.node_ag && A.node_g;
-    const int nn_lim = pub ? nd_nn : 0x7fffffff;
     if (tid < nk)  // (A.cur_g only with a Dict: mp_ha_expand has neither)
-      g_need[tid] = !A.dnid || !(hit >= 0 && hit < nn_lim && !((pub ? nd_g : A.cur_g[s]) + P.expand_time < gd));
+      g_need[tid] = !A.dnid || !(hit >= 0 && !(A.cur_g[s] + P.expand_time < gd));
     __syncthreads();
     HTIME(5);
     HSTAMP(14);
@@ -1456,16 +1328,7 @@ __device__ __forceinline__ bool ha_iter_body(const HaDev& P, const IterArgs& A, 
       const int jj = j < nk ? j : 0;
       change_basis_sc(g_nb[jj], goal, P.minR, g_sc[jj][0], g_sc[jj][1], ns);
       HTIME(2);
-      if (HA_FULL_TUV_CODE && A.full_tuv && A.hp_t) {  // (t, u, v) of each neighbour's winner, for RS_connected
-        double tv[3];
-        cb = rs_best_split<false, HWt, NoMid, true>(ns, tid, &best, red_c, red_i, nullptr, NoMid(), tv);
-        if ((lane & 3) == 0 && j < nk && (tid >> 6) == (best / 4) / (12 / HWt))
-#pragma unroll
-          for (int e = 0; e < 3; e++)
-            st_out(A.coherent, A.hp_t + ((size_t)s * P.n_prim + k0 + j) * 12 + e, tv[e]);
-      } else {
-        cb = rs_best_split<false, HWt>(ns, tid, &best, red_c, red_i);
-      }
+      cb = rs_best_split<false, HWt>(ns, tid, &best, red_c, red_i);
       HSTAMP(15);
       HTIME(3);
     }
@@ -1712,8 +1575,6 @@ struct HaSearch {
   double* otuv;          // [B][C][3] open entries: the same
   double* node_tuv;      // [2][B][3] popped node's, double-buffered like node
   long long* pre;        // [B][PRE_W] (RSH tail) the prescan's record: popfirst!'s K least entries before FindNewNode
-  double* node_g;        // [2][B] (full-width ha_pipe_kernel) the popped node's g, double-buffered like node
-  int* node_nn;          // [2][B] the scene's node count before the FindNewNode that published the node
   unsigned long long* ngr;  // [HA_NGR_SLOTS][B][HA_NGR] the popped node as tagged granules (ha_publish_node), by it & 3
   int* nx;               // [B] (ha_pipe_kernel) 2·it + 2 + go once iteration it's bookkeeping has popped the next node
   int* ex;               // [B] (ha_persist_kernel) expansions finished (neighbour groups, cumulative)
@@ -1784,15 +1645,14 @@ __device__ __forceinline__ void key_min_dpp(double& f, long long& sq, int& p) {
   }
 }
 
-// popfirst! for scene b (a 256-thread block): the least (f, seq) open entry, found by a
+// popfirst! for scene b (an NT-thread block): the least (f, seq) open entry, found by a
 // strided scan (4 independent entry loads in flight per thread) and a wave then block
 // reduction (the key order is total, so the reduction order does not matter); wave 0 removes
 // it by moving the last entry into its place.  Returns false (block-uniform) when the search
 // ends here (open list empty / max_pops).
 // NT threads (a multiple of 64).  The popped state goes to node_out[3 * b]; direct: the pop count and
-// pop_seq are written here (ha_init_kernel, ha_book_kernel), else they are left to the scene's finisher
+// pop_seq are written here (ha_init_kernel), else they are left to the scene's finisher
 // in ha_step_kernel and the popped Encode index is returned in *iw_out (lane 0 of wave 0).
-constexpr int BKT = 256;
 // TUV: the open entries carry the (t, u, v) of RSH-tail nodes (only the tail's launches can meet them: the shapes
 // go full width -> tail, never back)
 template <int NT, bool TUV = true>
@@ -2003,231 +1863,6 @@ __global__ __launch_bounds__(256) void ha_init_kernel(HaDev P, HaSearch Q, int B
   if (tid == 0) Q.sc_i[SI_ACTIVE * B + b] = go;
 }
 
-// One search iteration's bookkeeping for scene b, after ha_iter_kernel wrote the scene's
-// RS_connected result and the 62 neighbours (array mode): termination (:259-271) or
-// FindNewNode's Dict/open-list updates (:418-446) on wave 0 (neighbour k on lane k), then the
-// next popfirst! (whole block).
-__device__ void ha_book(const HaDev& P, const HaSearch& Q, const IterArgs& A, int B, int it, int b) {
-  __shared__ int s_nopen;
-  const int tid = threadIdx.x, lane = tid & 63;
-  BTIME(0);
-  const size_t base = (size_t)b * Q.C;
-  const int np = P.n_prim;
-  // one round of independent loads: the scene's counters and wave 0's neighbour record (lane k)
-  const int active = Q.sc_i[SI_ACTIVE * B + b];
-  const int rs_ok = A.rs_ok[b];
-  const int loop = Q.sc_i[SI_LOOP * B + b];
-  const int n_open0 = Q.sc_i[SI_NOPEN * B + b];
-  const int nn0 = Q.sc_i[SI_NNODES * B + b];
-  const long long ctr = Q.ctr[b];
-  const double cur_g = Q.cur_g[b];
-  const long long cidx = Q.cur_ix[b];
-  long long ix = 0;
-  int frk = 0, hwk = -1;
-  double hk = 0.0, nb0 = 0.0, nb1 = 0.0, nb2 = 0.0;
-  double tuvk[3] = {0.0, 0.0, 0.0};
-  if (tid < np) {
-    ix = A.idx[(size_t)b * np + tid];
-    frk = A.fr[(size_t)b * np + tid];
-    hk = A.h[(size_t)b * np + tid];
-    if (A.hw) hwk = A.hw[(size_t)b * np + tid];
-    nb0 = A.nb[((size_t)b * np + tid) * 3];
-    nb1 = A.nb[((size_t)b * np + tid) * 3 + 1];
-    nb2 = A.nb[((size_t)b * np + tid) * 3 + 2];
-  }
-  if (!active) return;
-  BTIME(1);
-  if (rs_ok) {  // RS_connected: path found -> hybrid_astar_states by the parent chain
-    if (tid == 0) {
-      Q.sc_i[SI_FOUND * B + b] = 1;
-      Q.sc_i[SI_ACTIVE * B + b] = 0;
-      Q.sc_i[SI_RSLEN * B + b] = A.rs_len[b];
-      double* so = Q.states + (size_t)b * Q.mp * 3;
-      int c = Q.sc_i[SI_CUR * B + b], ns = 0;
-      for (int r = 0; r < 3; r++) so[r] = Q.st[(base + c) * 3 + r];
-      ns++;
-      while (Q.parent[base + c] >= 0 && Q.index[base + c] != Q.start_index[b] && ns < Q.mp) {
-        const long long pc = Q.parent[base + c];
-        c = (pc >= 0 && pc < Q.C) ? Q.nid[base + pc] : -1;
-        if (c < 0) break;
-        for (int r = 0; r < 3; r++) so[3 * ns + r] = Q.st[(base + c) * 3 + r];
-        ns++;
-      }
-      Q.sc_i[SI_NSTATES * B + b] = ns;
-    }
-    return;
-  }
-  BTIME(2);
-  // ---- FindNewNode (:391-447): only the first valid occurrence of an Encode index in this
-  // expansion can change anything (every neighbour has the same tentative g).  Lane k of wave 0 is
-  // neighbour k; it is a duplicate when an earlier valid lane holds the same Encode index.  The 64
-  // comparisons per lane are split over the block's four waves (wave w: earlier lanes 16w..16w+15,
-  // broadcast LDS reads), while wave 0 already loads the Dict entries of its valid lanes (loads
-  // only: the Dict changes after the check), so their latency overlaps the check.
-  __shared__ long long s_vix[64];
-  __shared__ int s_dup[BKT / 64][64];
-  static_assert(BKT == 256, "the duplicate check below ORs four wave partials");
-  const bool valid = tid < np && ix != 0 && frk;
-  if (tid < 64) s_vix[tid] = valid ? ix : 0;
-  __syncthreads();
-  {
-    const int w = tid >> 6;
-    const long long key = s_vix[lane];  // lane's own index if valid, else 0 (never a duplicate then)
-    bool d = false;
-#pragma unroll
-    for (int jj = 0; jj < 16; jj++) {  // unconditional reads: no exec-masked branch per j
-      const int j = 16 * w + jj;
-      const long long oj = s_vix[j];
-      d = d | ((oj == key) & (j < lane) & (key != 0));
-    }
-    s_dup[w][lane] = d;
-  }
-  int hit = -1;
-  double gd = 0.0, fo_ = 0.0, dst0 = 0.0, dst1 = 0.0, dst2 = 0.0;
-  int po = 0, drw = -1;
-  double dtuv[3] = {0.0, 0.0, 0.0};
-  long long so0 = 0, io = 0;
-  if (valid) {  // wave 0: the Dict entry of every valid lane (used by the first occurrences below)
-    hit = (ix >= 0 && ix < Q.C) ? Q.nid[base + ix] : -1;
-    if (hit >= 0) {
-      gd = Q.g[base + hit];
-      po = Q.pos[base + hit];
-      fo_ = Q.f[base + hit];
-      so0 = Q.seq[base + hit];
-      io = Q.index[base + hit];
-      drw = Q.rw[base + hit];
-#pragma unroll
-      for (int e = 0; e < 3; e++) dtuv[e] = 0.0;  // (no RSH units in the split shape: no node has (t, u, v))
-      dst0 = Q.st[(base + hit) * 3];
-      dst1 = Q.st[(base + hit) * 3 + 1];
-      dst2 = Q.st[(base + hit) * 3 + 2];
-    }
-  }
-  BTIME(8);
-  __syncthreads();
-  if (tid < 64) {
-    int n_open = n_open0;
-    const int k = lane;
-    const bool dup = s_dup[0][k] | s_dup[1][k] | s_dup[2][k] | s_dup[3][k];
-    const bool first = valid && !dup;
-    BTIME(3);
-    const double tg = cur_g + P.expand_time;
-    double th = 0.0, tf = 0.0;
-    int id = -1;
-    bool chg = false, app = false, isnew = false;
-    double fo = 0.0;
-    long long so_ = 0;
-    double nst0 = 0.0, nst1 = 0.0, nst2 = 0.0;  // the node's state and Encode index (its open entry)
-    long long nix = ix;
-    int nrw = hwk;  // the node's stored rs_heuristic winner (its open entry carries it)
-    double nt0 = tuvk[0], nt1 = tuvk[1], nt2 = tuvk[2];
-    if (first) {
-      th = ha_temp_h(hk, 0.0);  // (ha_book_kernel serves no plan with use_astar)
-      tf = tg + th;
-      if (hit >= 0) {
-        id = hit;
-        nst0 = dst0;
-        nst1 = dst1;
-        nst2 = dst2;
-        nix = io;
-        nrw = drw;
-        nt0 = dtuv[0];
-        nt1 = dtuv[1];
-        nt2 = dtuv[2];
-        if (tg < gd) {
-          if (po >= 0) {
-            chg = true;
-            fo = fo_;
-            so_ = so0;
-          } else {
-            app = true;
-          }
-        }
-      } else {
-        isnew = true;
-        app = true;
-        nst0 = nb0;
-        nst1 = nb1;
-        nst2 = nb2;
-      }
-    }
-    BTIME(4);
-    const unsigned long long m_new = __ballot(isnew), m_chg = __ballot(chg), m_app = __ballot(app);
-    const unsigned long long below = (1ull << k) - 1;  // lanes < k
-    const int n_new = __popcll(m_new), n_chg = __popcll(m_chg), n_app = __popcll(m_app);
-    if (isnew) id = nn0 + __popcll(m_new & below);
-    // in-place updates keep their previous list order: rank by the old key among the changed
-    int r = 0;
-    for (unsigned long long m = m_chg; m; m &= m - 1) {
-      const int j = __builtin_ctzll(m);
-      const double fj = __shfl(fo, j);
-      const long long sj = __shfl(so_, j);
-      r += chg && key_before(fj, sj, fo, so_);
-    }
-    long long nseq = 0;
-    if (chg) nseq = ctr + r;
-    else if (app) nseq = ctr + n_chg + __popcll(m_app & below);  // then push! in neighbour order
-    if (chg || app) {
-      const size_t q = base + id;
-      if (isnew) {
-        Q.st[q * 3] = nst0;
-        Q.st[q * 3 + 1] = nst1;
-        Q.st[q * 3 + 2] = nst2;
-        Q.index[q] = ix;
-        Q.rw[q] = nrw;
-        if (ix > 0 && ix < Q.C) Q.nid[base + ix] = id;
-      }
-      Q.g[q] = tg;
-      Q.h[q] = th;
-      Q.f[q] = tf;
-      Q.parent[q] = cidx;
-      Q.seq[q] = nseq;
-      const int p = chg ? Q.pos[q] : n_open + __popcll(m_app & below);
-      Q.of[base + p] = tf;
-      Q.oseq[base + p] = nseq;
-      Q.og[base + p] = tg;
-      if (!chg) {
-        Q.oid[base + p] = id;
-        Q.oix[base + p] = nix;
-        Q.orw[base + p] = nrw;
-        Q.ost[(base + p) * 3] = nst0;
-        Q.ost[(base + p) * 3 + 1] = nst1;
-        Q.ost[(base + p) * 3 + 2] = nst2;
-        Q.pos[q] = p;
-      }
-    }
-    n_open += n_app;
-    if (lane == 0) {
-      Q.sc_i[SI_NNODES * B + b] = nn0 + n_new;
-      Q.ctr[b] = ctr + n_chg + n_app;
-      s_nopen = n_open;
-    }
-  }
-  BTIME(5);
-  __syncthreads();  // the open-list writes of wave 0 before the block-wide scan
-  BTIME(6);
-  const int n_open = s_nopen;
-  // ---- next popfirst!
-  const bool go = ha_pop<BKT, false>(Q, B, b, n_open, loop, tid, Q.node + (size_t)(it & 1) * 3 * B, Q.node_rw + (size_t)(it & 1) * B,
-                            Q.node_tuv + (size_t)(it & 1) * 3 * B, true,
-                            nullptr);
-  BTIME(7);
-  if (tid == 0) {
-    if (go) Q.lst[(it & 1) * B + atomicAdd(Q.live + it, 1)] = b;
-    else {
-      Q.sc_i[SI_ACTIVE * B + b] = 0;
-      Q.sc_i[SI_NOPEN * B + b] = n_open;
-    }
-  }
-}
-
-__global__ __launch_bounds__(BKT) void ha_book_kernel(HaDev P, HaSearch Q, IterArgs A, int B, int it) {
-  // the scenes live entering this iteration: the list the previous iteration's bookkeeping wrote
-  // (iteration 1: every scene, inactive ones return at once)
-  if (A.n_live && (int)blockIdx.x >= *A.n_live) return;
-  ha_book(P, Q, A, B, it, A.scene_of ? A.scene_of[blockIdx.x] : (int)blockIdx.x);
-}
-
 // ---------------------------------------------------------------- fused iteration (ha_step_kernel)
 // One launch per search iteration does the expansion AND the bookkeeping.  FindNewNode (:418-446) and
 // the next popfirst! need only the 62 neighbour records, not RS_connected's answer, so the last of a
@@ -2245,17 +1880,15 @@ __global__ __launch_bounds__(BKT) void ha_book_kernel(HaDev P, HaSearch Q, IterA
 __device__ __forceinline__ void ha_stores_done() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 enum { RC_GO = 0, RC_LOOP, RC_NN0, RC_NNEW, RC_NOPEN, RC_CUR, RC_IW, RC_N = 8 };
-#ifndef HA_FIN_SHORTCUT
-#define HA_FIN_SHORTCUT 1  // the bookkeeping block arriving second finishes with its own values
-#endif
 // the bookkeeping's results for the scene's finisher (valid in thread 0)
 struct BookRec {
   long long v[RC_N];
 };
 
-// FindNewNode + popfirst! for scene b on an NT-thread block (ha_book without its termination branch):
-// the neighbour records are read agent-coherently; the node count, the pop count and pop_seq go to the
-// scene's record (Q.rec) for the finisher instead of the scene's counters.
+// FindNewNode's Dict / open-list updates (:418-446) on wave 0 (neighbour k on lane k) + the next popfirst!
+// (whole block) for scene b on an NT-thread block: the neighbour records are read agent-coherently; the node
+// count, the pop count and pop_seq go to the scene's record (Q.rec) for the finisher (ha_finish, which also
+// holds the termination of :259-271) instead of the scene's counters.
 template <int NT, bool RSH = false, bool AST = false>
 __device__ __forceinline__ BookRec ha_book_spec(const HaDev& P, const HaSearch& Q, const IterArgs& A, int B, int it,
                                                 int b, unsigned long long* stp = nullptr) {
@@ -2311,11 +1944,6 @@ __device__ __forceinline__ BookRec ha_book_spec(const HaDev& P, const HaSearch& 
     } else {
       hk = ld_ag(A.h + q);
       if (A.hw) hwk = ld_ag(A.hw + q);
-      if (A.full_tuv && hwk >= 0) {  // (the groups stored the winner's (t, u, v))
-        hwk |= RW_TUV | (hk < __builtin_inf() ? RW_OK : 0);
-#pragma unroll
-        for (int e = 0; e < 3; e++) tuvk[e] = ld_ag(A.hp_t + q * 12 + e);
-      }
     }
     nb0 = ld_ag(A.nb + 3 * q);
     nb1 = ld_ag(A.nb + 3 * q + 1);
@@ -2342,7 +1970,9 @@ __device__ __forceinline__ BookRec ha_book_spec(const HaDev& P, const HaSearch& 
     }
   }
   // duplicates: lane k of wave 0 is neighbour k; an earlier valid lane with the same Encode index makes
-  // it one (the comparisons split over four waves, as in ha_book)
+  // it one.  Only the first valid occurrence of an Encode index in this expansion can change anything (every
+  // neighbour has the same tentative g).  The 64 comparisons per lane are split over four waves (wave w: earlier
+  // lanes 16w..16w+15, broadcast LDS reads, unconditional: no exec-masked branch per j)
   const bool valid = tid < np && ix != 0 && frk;
   if (tid < 64) s_vix[tid] = valid ? ix : 0;
   __syncthreads();
@@ -2363,24 +1993,7 @@ __device__ __forceinline__ BookRec ha_book_spec(const HaDev& P, const HaSearch& 
   int po = 0, drw = -1;
   double dtuv[3] = {0.0, 0.0, 0.0};
   long long so0 = 0, io = 0;
-  if (HA_DREC_CODE && valid && !RSH && A.drec && A.dnid) {  // the groups' copies of the Dict entries
-    const long long* r = A.drec + ((size_t)b * np + tid) * HA_DREC;
-    long long w[HA_DREC];
-#pragma unroll
-    for (int e = 0; e < HA_DREC; e++) w[e] = ld_ag(r + e);
-    hit = (int)w[0];
-    if (hit >= 0) {
-      gd = __longlong_as_double(w[1]);
-      po = (int)w[2];
-      fo_ = __longlong_as_double(w[3]);
-      so0 = w[4];
-      io = w[5];
-      drw = (int)w[6];
-      dst0 = __longlong_as_double(w[7]);
-      dst1 = __longlong_as_double(w[8]);
-      dst2 = __longlong_as_double(w[9]);
-    }
-  } else if (valid) {
+  if (valid) {  // wave 0: the Dict entry of every valid lane (loads only: the Dict changes after the check)
     hit = (ix >= 0 && ix < Q.C) ? Q.nid[base + ix] : -1;
     if (hit >= 0) {
       gd = Q.g[base + hit];
@@ -2390,7 +2003,7 @@ __device__ __forceinline__ BookRec ha_book_spec(const HaDev& P, const HaSearch& 
       io = Q.index[base + hit];
       drw = Q.rw[base + hit];
 #pragma unroll
-      for (int e = 0; e < 3; e++) dtuv[e] = (RSH || HA_FULL_TUV_CODE) ? Q.tuv[(base + hit) * 3 + e] : 0.0;
+      for (int e = 0; e < 3; e++) dtuv[e] = RSH ? Q.tuv[(base + hit) * 3 + e] : 0.0;
       dst0 = Q.st[(base + hit) * 3];
       dst1 = Q.st[(base + hit) * 3 + 1];
       dst2 = Q.st[(base + hit) * 3 + 2];
@@ -2465,7 +2078,7 @@ __device__ __forceinline__ BookRec ha_book_spec(const HaDev& P, const HaSearch& 
         Q.st[q * 3 + 2] = nst2;
         Q.index[q] = ix;
         Q.rw[q] = nrw;
-        if (RSH || HA_FULL_TUV_CODE) {
+        if (RSH) {
           Q.tuv[q * 3] = nt0;
           Q.tuv[q * 3 + 1] = nt1;
           Q.tuv[q * 3 + 2] = nt2;
@@ -2485,7 +2098,7 @@ __device__ __forceinline__ BookRec ha_book_spec(const HaDev& P, const HaSearch& 
         Q.oid[base + p] = id;
         Q.oix[base + p] = nix;
         Q.orw[base + p] = nrw;
-        if (RSH || HA_FULL_TUV_CODE) {
+        if (RSH) {
           Q.otuv[(base + p) * 3] = nt0;
           Q.otuv[(base + p) * 3 + 1] = nt1;
           Q.otuv[(base + p) * 3 + 2] = nt2;
@@ -2659,8 +2272,7 @@ __device__ __forceinline__ BookRec ha_book_spec(const HaDev& P, const HaSearch& 
     go = s_merged == 1;
     iw = s_iw;
   } else {
-    // (HA_FULL_TUV_CODE: the commands travel with the entry in both shapes, a full-width winner's rw carries RW_TUV)
-    go = ha_pop<NT, RSH || HA_FULL_TUV_CODE>(Q, B, b, n_open, loop, tid, Q.node + (size_t)(it & 1) * 3 * B, Q.node_rw + (size_t)(it & 1) * B,
+    go = ha_pop<NT, RSH>(Q, B, b, n_open, loop, tid, Q.node + (size_t)(it & 1) * 3 * B, Q.node_rw + (size_t)(it & 1) * B,
                     Q.node_tuv + (size_t)(it & 1) * 3 * B, false, &iw, stp);
   }
   BSTAMP(8);
@@ -2901,8 +2513,6 @@ __device__ __forceinline__ IterArgs e_par(const IterArgs& A, int B, int np, int 
   E.hp_c = A.hp_c + 4 * n;
   E.hp_i = A.hp_i + 4 * n;
   E.hp_t = A.hp_t + 12 * n;
-  E.h = A.h + n;  // (full-width pipe) rs_heuristic and its winner per neighbour
-  E.hw = A.hw ? A.hw + n : nullptr;
   return E;
 }
 
@@ -2914,7 +2524,10 @@ __device__ __forceinline__ IterArgs e_par(const IterArgs& A, int B, int np, int 
 // (10 payload words + valid), and the pop's go word carries skip = hit (the popped node IS the previous
 // runner-up, identical id, state and stored commands: its expansion and RS_connected were made speculatively);
 // *hit_out returns it.
-template <int NT, bool RSH = true, class Wait = NoMid, bool SPEC = false, bool AST = false>
+struct NoWait {
+  __device__ void operator()() const {}
+};
+template <int NT, class Wait = NoWait, bool SPEC = false, bool AST = false>
 __device__ __forceinline__ BookRec ha_book_pipe(const HaDev& P, const HaSearch& Q, const IterArgs& E, int B, int it,
                                                 int b, unsigned long long* stp = nullptr, const Wait& pre_wait = Wait(),
                                                 long long* sr = nullptr, int* hit_out = nullptr) {
@@ -2965,7 +2578,7 @@ __device__ __forceinline__ BookRec ha_book_pipe(const HaDev& P, const HaSearch& 
     const size_t q = (size_t)b * np + tid;
     ix = ld_ag(E.idx + q);
     frk = ld_ag(E.fr + q);
-    if (RSH) {
+    {  // rs_heuristic from its four word chunks, as ha_book_spec<NT, true>
       double cv[4], ct[4][3];
       int ci[4];
 #pragma unroll
@@ -2989,14 +2602,6 @@ __device__ __forceinline__ BookRec ha_book_pipe(const HaDev& P, const HaSearch& 
         if (wc == c)
 #pragma unroll
           for (int e = 0; e < 3; e++) tuvk[e] = ct[c][e];
-    } else {  // the full-width groups' own rs_heuristic and winner (as ha_book_spec<NT, false>)
-      hk = ld_ag(E.h + q);
-      if (E.hw) hwk = ld_ag(E.hw + q);
-      if (E.full_tuv && hwk >= 0) {
-        hwk |= RW_TUV | (hk < __builtin_inf() ? RW_OK : 0);
-#pragma unroll
-        for (int e = 0; e < 3; e++) tuvk[e] = ld_ag(E.hp_t + q * 12 + e);
-      }
     }
     nb0 = ld_ag(E.nb + 3 * q);
     nb1 = ld_ag(E.nb + 3 * q + 1);
@@ -3222,7 +2827,7 @@ __device__ __forceinline__ BookRec ha_book_pipe(const HaDev& P, const HaSearch& 
 #pragma unroll
       for (int e = 3; e < 10; e++) hit = hit && s_win[e] == sr[e];
     }
-    if (RSH && E.ngr_pub) {
+    if (E.ngr_pub) {
       // publish the next node as tagged granules (ha_publish_node): no drain, no separate flag; the node
       // buffers too, for the next launch's RS_connected (a launch boundary orders those)
       long long wv[10];
@@ -3243,8 +2848,6 @@ __device__ __forceinline__ BookRec ha_book_pipe(const HaDev& P, const HaSearch& 
           st_ag(Q.node_tuv + (size_t)(it & 1) * 3 * B + 3 * b + lane, __longlong_as_double(s_win[7 + lane]));
         }
         if (lane == 0) st_ag(Q.node_rw + (size_t)(it & 1) * B + b, (int)s_win[6]);
-        if (!RSH && lane == 1) st_ag(Q.node_g + (size_t)(it & 1) * B + b, __longlong_as_double(s_win[1]));
-        if (!RSH && lane == 2) st_ag(Q.node_nn + (size_t)(it & 1) * B + b, nn0);
       }
       ha_stores_done();
       if (lane == 0) st_ag(Q.nx + b, 2 * it + 2 + (go ? 1 : 0));
@@ -3527,21 +3130,6 @@ __global__ __launch_bounds__(64 * HWt) __attribute__((amdgpu_waves_per_eu(HWt ==
   long long* rc = Q.rec + (size_t)RC_N * s;
   if (r == 1) {
     const BookRec br = ha_book_spec<64 * HWt, RSH, AST>(P, Q, A, B, it, s, stp);
-    if (!HA_FIN_SHORTCUT) {  // (A/B) always publish the record first
-      if (threadIdx.x == 0) {
-#pragma unroll
-        for (int i = 0; i < RC_N - 1; i++) st_ag(rc + i, br.v[i]);
-        ha_stores_done();
-        st_ag(rc + RC_N - 1, 1LL);
-        if (__hip_atomic_fetch_add(Q.tk + B + s, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 1) {
-          asm volatile("" ::: "memory");
-          st_ag(Q.tk + B + s, 0);
-          st_ag(rc + RC_N - 1, 0LL);
-          ha_finish(Q, A, B, it, s, br);
-        }
-      }
-      return;
-    }
     if (threadIdx.x == 0) {
       if (stp) __hip_atomic_store(stp + 3, __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (__hip_atomic_fetch_add(Q.tk + B + s, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 1) {
@@ -3577,8 +3165,8 @@ __global__ __launch_bounds__(64 * HWt) __attribute__((amdgpu_waves_per_eu(HWt ==
 // ha_pipe_kernel: the pipelined tail's launch (see above).  Items per slot: 0 RS_connected(n_it), 1 the
 // bookkeeping, 2 .. 1 + n_groups the expansion of n_{it+1}.  boot = 1: only the expansion, of n_it itself
 // (node buffer (it - 1) & 1) into E[it & 1], for the first pipelined launch.
-template <int HWt, int NBGt, bool RSH = true, bool AST = false>
-__global__ __launch_bounds__(64 * HWt) __attribute__((amdgpu_waves_per_eu(HWt == 4 ? HA_WPE_FULL : HA_WPE_TAIL))) void ha_pipe_kernel(
+template <int HWt, int NBGt, bool AST = false>
+__global__ __launch_bounds__(64 * HWt) __attribute__((amdgpu_waves_per_eu(HA_WPE_TAIL))) void ha_pipe_kernel(
     HaDev P, HaSearch Q, IterArgs A, int B, int it, int boot) {
   __shared__ int role, sh_go;
   unsigned long long* stp = nullptr;
@@ -3602,16 +3190,13 @@ __global__ __launch_bounds__(64 * HWt) __attribute__((amdgpu_waves_per_eu(HWt ==
       X.node_flag = Q.nx;
       X.node_flag_min = 2 * it + 2;
       X.node_flag_err = Q.err;
-      if (!RSH) {  // the Dict pre-check beside FindNewNode's writes (ha_iter_body)
-        X.node_g = Q.node_g + (size_t)(it & 1) * B;
-        X.node_nn = Q.node_nn + (size_t)(it & 1) * B;
-      } else if (A.ngr_pub) {  // the node as tagged granules
+      if (A.ngr_pub) {  // the node as tagged granules
         X.ngr = Q.ngr + (size_t)(it & (HA_NGR_SLOTS - 1)) * B * HA_NGR;
         X.ngr_tag = (unsigned)it + 1;
       }
     }
     X.do_rs = 0;
-    ha_iter_body<HWt, NBGt, RSH>(P, X, stp, slot, item - 1);
+    ha_iter_body<HWt, NBGt, true>(P, X, stp, slot, item - 1);
     if (stp) {
       __hip_atomic_store(stp + 1, __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __hip_atomic_store(stp + 5, ((unsigned long long)s << 4) | ((unsigned long long)(item - 1) << 32), __ATOMIC_RELAXED,
@@ -3621,7 +3206,7 @@ __global__ __launch_bounds__(64 * HWt) __attribute__((amdgpu_waves_per_eu(HWt ==
   }
   if (boot) return;
   if (item == 0) {
-    if (!ha_iter_body<HWt, NBGt, RSH>(P, A, stp, slot, 0)) return;
+    if (!ha_iter_body<HWt, NBGt, true>(P, A, stp, slot, 0)) return;
     ha_stores_done();
     __syncthreads();
   }
@@ -3632,7 +3217,7 @@ __global__ __launch_bounds__(64 * HWt) __attribute__((amdgpu_waves_per_eu(HWt ==
   // the final ticket: RS_connected (item 0) and the bookkeeping (item 1), as in ha_step_kernel
   long long* rc = Q.rec + (size_t)RC_N * s;
   if (item == 1) {
-    const BookRec br = ha_book_pipe<64 * HWt, RSH, NoMid, false, AST>(P, Q, e_par(A, B, np, it & 1), B, it, s, stp);
+    const BookRec br = ha_book_pipe<64 * HWt, NoWait, false, AST>(P, Q, e_par(A, B, np, it & 1), B, it, s, stp);
     if (threadIdx.x == 0) {
       if (stp) __hip_atomic_store(stp + 3, __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (__hip_atomic_fetch_add(Q.tk + B + s, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 1) {
@@ -3827,14 +3412,10 @@ __global__ __launch_bounds__(64 * HWt) __attribute__((amdgpu_waves_per_eu(HWt ==
     };
     const IterArgs Ei = e_par(A, B, np, h ? 2 + ((it - 1) & 3) : it & 1);
     int hit_next = 0;
-#ifndef HA_PREWAIT
-#define HA_PREWAIT 1
-#endif
-    if (!HA_PREWAIT) wait_exp();  // (A/B build -DHA_PREWAIT=0: the wait before the bookkeeping's first load)
-    const BookRec br = HA_PREWAIT ? ha_book_pipe<NTB, true, decltype(wait_exp), SPEC, AST>(P, Q, Ei, B, it, s, stp,
-                                                                                 wait_exp, sh_run, &hit_next)
-                                  : ha_book_pipe<NTB, true, NoMid, SPEC, AST>(P, Q, Ei, B, it, s, stp, NoMid(), sh_run,
-                                                                   &hit_next);
+    // (the wait before the bookkeeping's first load instead of behind its open-list loads measured slower,
+    // profiles/r05ze_ha_persist_prewait_ab.txt)
+    const BookRec br =
+        ha_book_pipe<NTB, decltype(wait_exp), SPEC, AST>(P, Q, Ei, B, it, s, stp, wait_exp, sh_run, &hit_next);
     put(stp, 3, now());
     IterArgs F = A;
     rs_slot(F, h ? 2 + ((it - 1) & 3) : it & 1);
@@ -4271,7 +3852,7 @@ int mp_ha_plan_astar(mp_ctx* ctx, const mp_ha_params* p, int32_t B, const double
   // search state: node arrays and open list indexed [scene][node / cell]
   const size_t per_cell = 8 + 24 + 8 + 24 + 8 + 4 + 4 + 8 + 8 + 4 + 8 + 8 + 24 + 4 + 4 + 24 + 24;
   char* ws = (char*)mp_ws(ctx, WS_HA2, nB * C * per_cell + nB * (SI_N * 4 + 32) + nB * mp * 32 + nB * 48 +
-                                           sizeof(int) * (mp + 2) + sizeof(int) * 4 * nB + nB * RC_N * 8 + nB * 8 + nB * 48 + nB * PRE_W * 8 + nB * 16 + 4 + nB * 24 + nB * HA_NGR_SLOTS * HA_NGR * 8 + 256 * 57 +
+                                           sizeof(int) * (mp + 2) + sizeof(int) * 4 * nB + nB * RC_N * 8 + nB * 8 + nB * 48 + nB * PRE_W * 8 + nB * 16 + 4 + nB * HA_NGR_SLOTS * HA_NGR * 8 + 256 * 57 +
                                            nB * HA_NGR_SLOTS * HA_NGR * 8 + nB * 24 + 256 * 4);
   if (!ws) return MP_ERR_NOMEM;
   size_t off = 0;
@@ -4318,8 +3899,6 @@ int mp_ha_plan_astar(mp_ctx* ctx, const mp_ha_params* p, int32_t B, const double
   Q.ex = (int*)take(nB * 4);
   Q.rsr = (int*)take(nB * 8);
   Q.err = (int*)take(AS_HDR + 3 * sizeof(double));  // the flag, and (mp_ha_plan_astar) the table header behind it
-  Q.node_g = (double*)take(nB * 16);
-  Q.node_nn = (int*)take(nB * 8);
   Q.ngr2 = (unsigned long long*)take(nB * HA_NGR_SLOTS * HA_NGR * 8);
   Q.exs = (int*)take(nB * 8);
   Q.rsrs = (int*)take(nB * 8);
@@ -4354,11 +3933,6 @@ int mp_ha_plan_astar(mp_ctx* ctx, const mp_ha_params* p, int32_t B, const double
   A.hw = (int*)mp_ws(ctx, WS_IO9, sizeof(int) * nB * np * NPAR);
   if (st || !A.h || !A.nb || !A.idx || !A.fr || !A.rs_ok || !A.rs_len || !A.rs_path || !A.hw)
     return st ? st : MP_ERR_NOMEM;
-#ifndef HA_RS_WINNER
-#define HA_RS_WINNER 1
-#endif
-  // (A/B build -DHA_RS_WINNER=0: RS_connected always runs the 48-candidate search)
-  constexpr bool rs_full = !HA_RS_WINNER;
   // the pose table (A.ptab): the neighbour sweeps' heading terms for every lattice heading -- regulated
   // headings are round(modπ(ψ)/res)·res, so m spans round(±π/res) (one spare step each side); the few
   // microseconds of one launch per plan.
@@ -4400,14 +3974,6 @@ int mp_ha_plan_astar(mp_ctx* ctx, const mp_ha_params* p, int32_t B, const double
   A.coherent = 1;
   A.dnid = Q.nid;  // the Dict pre-check: groups skip rs_heuristic when no neighbour of theirs can use it
   A.dg = Q.g;
-  // (A/B build -DHA_DREC_CODE=1) the groups' Dict records
-  A.drec = HA_DREC_CODE ? (long long*)mp_ws(ctx, WS_HA4, sizeof(long long) * nB * np * HA_DREC) : nullptr;
-  A.dpos = Q.pos;
-  A.df = Q.f;
-  A.dseq = Q.seq;
-  A.dindex = Q.index;
-  A.drw = Q.rw;
-  A.dst = Q.st;
   A.cur_g = Q.cur_g;
   A.C = (int)C;
   static const bool stamps_on = HA_STAMP_CODE && getenv("MPGPU_HA_STAMPS") && atoi(getenv("MPGPU_HA_STAMPS")) == 1;
@@ -4534,8 +4100,8 @@ int mp_ha_plan_astar(mp_ctx* ctx, const mp_ha_params* p, int32_t B, const double
   A.rs_last = true;  // RS_connected blocks dispatched after the groups (r05o: -0.2 ms)
   A.no_tuv = false;  // the tail stores the winners' (t, u, v): RS_connected rebuilds the commands from them
   A.ngr_pub = true;  // the popped node handed over as tagged granules (r05zl)
-  // (A/B build -DHA_FULL_TUV_CODE=1) the full-width groups' winners' (t, u, v) too (neutral per plan, r05u)
-  A.full_tuv = HA_FULL_TUV_CODE;
+  // (the full-width groups storing their winners' (t, u, v) too measured neutral per plan,
+  // profiles/r05u_ha_fulltuv_mirror_fpipe_ab.txt)
   if (!A.hp_c || !A.hp_i || !A.hp_t) return MP_ERR_NOMEM;
   // iteration it >= 2 works on the compact list of scenes still live (written by the previous
   // bookkeeping launch, count on the device); the host sizes the grids by the last live count it has
@@ -4564,7 +4130,7 @@ int mp_ha_plan_astar(mp_ctx* ctx, const mp_ha_params* p, int32_t B, const double
     A.n_live = it == 1 ? nullptr : Q.live + (it - 1);
     A.n_active = known;
     A.node = Q.node + (size_t)((it - 1) & 1) * 3 * B;  // the previous iteration's pops
-    A.node_rw = rs_full ? nullptr : Q.node_rw + (size_t)((it - 1) & 1) * B;
+    A.node_rw = Q.node_rw + (size_t)((it - 1) & 1) * B;
     A.node_tuv = Q.node_tuv + (size_t)((it - 1) & 1) * 3 * B;
     const bool tail = known * per_tail <= tail_blocks;
     if (tail_pipe && known * per_ps <= persist_cap) {
@@ -4572,7 +4138,7 @@ int mp_ha_plan_astar(mp_ctx* ctx, const mp_ha_params* p, int32_t B, const double
       const int per_pipe = 2 + (np + NBG_TAIL - 1) / NBG_TAIL;
       if (piped != 2) {
         if (use_astar)
-          hipLaunchKernelGGL((ha_pipe_kernel<HW_TAIL, NBG_TAIL, true, true>), dim3((unsigned)(known * per_pipe)), dim3(64 * HW_TAIL),
+          hipLaunchKernelGGL((ha_pipe_kernel<HW_TAIL, NBG_TAIL, true>), dim3((unsigned)(known * per_pipe)), dim3(64 * HW_TAIL),
                              0, ctx->stream, D, Q, A, B, it, 1);
         else
           hipLaunchKernelGGL((ha_pipe_kernel<HW_TAIL, NBG_TAIL>), dim3((unsigned)(known * per_pipe)), dim3(64 * HW_TAIL),
@@ -4606,7 +4172,7 @@ int mp_ha_plan_astar(mp_ctx* ctx, const mp_ha_params* p, int32_t B, const double
       const int per_pipe = 2 + (np + NBG_TAIL - 1) / NBG_TAIL;
       if (piped != 2) {  // the current nodes' expansion, for the first pipelined launch
         if (use_astar)
-          hipLaunchKernelGGL((ha_pipe_kernel<HW_TAIL, NBG_TAIL, true, true>), dim3((unsigned)(known * per_pipe)), dim3(64 * HW_TAIL),
+          hipLaunchKernelGGL((ha_pipe_kernel<HW_TAIL, NBG_TAIL, true>), dim3((unsigned)(known * per_pipe)), dim3(64 * HW_TAIL),
                              0, ctx->stream, D, Q, A, B, it, 1);
         else
           hipLaunchKernelGGL((ha_pipe_kernel<HW_TAIL, NBG_TAIL>), dim3((unsigned)(known * per_pipe)), dim3(64 * HW_TAIL),
@@ -4614,7 +4180,7 @@ int mp_ha_plan_astar(mp_ctx* ctx, const mp_ha_params* p, int32_t B, const double
         piped = 2;
       }
       if (use_astar)
-        hipLaunchKernelGGL((ha_pipe_kernel<HW_TAIL, NBG_TAIL, true, true>), dim3((unsigned)(known * per_pipe)), dim3(64 * HW_TAIL), 0,
+        hipLaunchKernelGGL((ha_pipe_kernel<HW_TAIL, NBG_TAIL, true>), dim3((unsigned)(known * per_pipe)), dim3(64 * HW_TAIL), 0,
                            ctx->stream, D, Q, A, B, it, 0);
       else
         hipLaunchKernelGGL((ha_pipe_kernel<HW_TAIL, NBG_TAIL>), dim3((unsigned)(known * per_pipe)), dim3(64 * HW_TAIL), 0,

@@ -190,9 +190,16 @@ def _plan_scenes(use_astar):
             ] + ha.scenario_batch(4, seed=4, use_astar=use_astar)
 
 
+def _tail_step_scenes():
+    """15 scenes: with MPGPU_HA_PERSIST=0 one too many for the pipelined tail, so the non-pipelined tail step
+    (ha_step_kernel<12, 4, true, true>) runs them until a live-count poll reports 14 or fewer."""
+    return ha.scenario_batch(13, seed=4, use_astar=True) + [ha.driver_searcher(ha.PERPENDICULAR, use_astar=True),
+                                                            ha.driver_searcher(ha.PARALLEL, use_astar=True)]
+
+
 @functools.lru_cache(maxsize=None)
-def plan_refs():
-    hs = _plan_scenes(True)
+def plan_refs(tail_step=False):
+    hs = _tail_step_scenes() if tail_step else _plan_scenes(True)
     p = ha.params_of(hs[0])
     sc, pc = oracle.ha_neighbor_origin(hs[0].s.expand_time, hs[0].s.steer_set, hs[0].s.gear_set)
     out = []
@@ -225,6 +232,18 @@ def test_ha_plan_astar_bitexact(ctx, persist):
     finally:
         if not persist:
             del os.environ["MPGPU_HA_PERSIST"]
+    _check_plans(hs, refs)
+
+
+def test_ha_plan_astar_tail_step_bitexact(ctx):
+    """The 15-scene batch with the persistent launch off: the tail step's use_astar instance."""
+    hs = _tail_step_scenes()
+    refs = plan_refs(True)
+    os.environ["MPGPU_HA_PERSIST"] = "0"
+    try:
+        ha.plan_batch(hs, ctx=ctx)
+    finally:
+        del os.environ["MPGPU_HA_PERSIST"]
     _check_plans(hs, refs)
 
 

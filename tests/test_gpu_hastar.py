@@ -90,8 +90,19 @@ def test_pipelined_tail_without_persistent_launch_bitexact(ctx):
     takes, or a refused cooperative launch falls back to; MPGPU_HA_PERSIST=0 selects it): bit-exact, and its
     bounded cross-block waits report through the same error flag the persistent tail's do (mp_ha_plan
     checks it after any pipelined launch and fails loudly)."""
+    _check_without_persistent_launch(ctx, 12)
+
+
+def test_tail_step_without_persistent_launch_bitexact(ctx):
+    """Exactly 15 scenes with MPGPU_HA_PERSIST=0: one too many for the pipelined tail (14), so the search starts
+    in the non-pipelined tail step (ha_step_kernel<12, 4, true>) and stays there until a live-count poll reports
+    14 or fewer scenes; bit-exact like every other shape."""
+    _check_without_persistent_launch(ctx, 13)
+
+
+def _check_without_persistent_launch(ctx, n):
     import os
-    hs = ha.scenario_batch(12, seed=4) + [ha.driver_searcher(ha.PERPENDICULAR), ha.driver_searcher(ha.PARALLEL)]
+    hs = ha.scenario_batch(n, seed=4) + [ha.driver_searcher(ha.PERPENDICULAR), ha.driver_searcher(ha.PARALLEL)]
     _, p, sc, pc = _setup(ctx)
     os.environ["MPGPU_HA_PERSIST"] = "0"
     try:

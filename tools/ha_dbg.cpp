@@ -1,5 +1,5 @@
 // Standalone Hybrid A* driver for kernel debugging and phase timing (s_memtime stamps of the RS_connected
-// block, the expansion blocks and one mid-search bookkeeping launch).  Build:
+// block and the expansion blocks).  Build:
 //   bash tools/build_variant.sh dbg "-DHA_DEBUG"
 //   hipcc --offload-arch=gfx950 -O2 -std=c++17 -o tools/ha_dbg tools/ha_dbg.cpp -Lmotionplanning_amd/lib \
 //         -lmpgpu_dbg -Wl,-rpath,'$ORIGIN/../motionplanning_amd/lib'
@@ -72,28 +72,6 @@ int main() {
       for (int i = 1; i < 16; i++) printf(" [%d]%lld", i, t[blk * 16 + i] ? (long long)(t[blk * 16 + i] - t[blk * 16]) : -1LL);
       printf("\n");
     }
-  }
-  {  // a short plan of the same scene: phase stamps of the last bookkeeping launch (scene 0)
-    memset(buf, 0, 1 << 20);
-    p.max_pops = 40;
-    const double start[3] = {7, 0, M_PI / 2};
-    int32_t found, pops, nn, ns, rl;
-    static int64_t seq[40];
-    static double st[40 * 3], rs[501 * 3];
-    printf("plan %d\n", mp_ha_plan(ctx, &p, 1, start, goal, walls, &found, &pops, &nn, seq, &ns, st, &rl, rs));
-    const unsigned long long* t = reinterpret_cast<const unsigned long long*>(buf + 64 * 64) + 4096 * 16;
-    printf("book stamps (cycles from [0]):");
-    for (int i = 1; i < 16; i++) printf(" [%d]%lld", i, t[i] ? (long long)(t[i] - t[0]) : -1LL);
-    printf("\npops %d\n", pops);
-    // the same after 600 pops (an open list of ~2,000 entries, as late in configs[3]'s longest searches)
-    memset(buf, 0, 1 << 20);
-    p.max_pops = 600;
-    static int64_t seq6[600];
-    static double st6[600 * 3];
-    printf("plan %d\n", mp_ha_plan(ctx, &p, 1, start, goal, walls, &found, &pops, &nn, seq6, &ns, st6, &rl, rs));
-    printf("book stamps at pop %d, %d nodes (cycles from [0]):", pops, nn);
-    for (int i = 1; i < 16; i++) printf(" [%d]%lld", i, t[i] ? (long long)(t[i] - t[0]) : -1LL);
-    printf("\n");
   }
   mp_ctx_destroy(ctx);
   return 0;
