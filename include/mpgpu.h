@@ -448,6 +448,45 @@ int mp_astar_plan(mp_ctx* ctx, int32_t B, int32_t nx, int32_t ny, const double* 
                   double* final_cost, int32_t* found, int32_t* pops, int32_t* n_nodes, int32_t* pop_seq,
                   int32_t* astarpath, int32_t* path_n, double* path_length);
 
+/* ------------------------------------------------- grid Dijkstra and BFS */
+/* planDKA! (PathPlanning/Dijkstra/src/dka_utils.jl:69-126 with FindNewNode :175-215) for B independent
+ * searches on nx x ny grids (defineDKA, Dijkstra/src/setup.jl:3-25): planAstar! without the heuristic.  The
+ * nine-entry direction list, the stable sort of the open list every iteration, the in-place update and the
+ * InOpen rule are mp_astar_plan's; the update test is on f (:193), which with no heuristic is the cost from
+ * the start.  One wavefront per search, grid limits and pop bound (MP_ERR_NUMERIC) as for mp_astar_plan.
+ * in : bound[B][4], start_real[B][2], goal_real[B][2] as for mp_astar_plan;
+ *      circles[B][n_obs][3] ([x, y, r]: checkObsSafety :233-243, strict <); NULL iff n_obs == 0 -- the
+ *      reference's loop runs over 1:0 then, every cell is free.
+ * out: final_cost[B] (the popped goal node's f), found[B], pops[B] (loop_count), n_nodes[B].
+ * optional (NULL: not returned):
+ *      pop_seq[B][2*(nx*ny+1)]  Encode index of every popped cell, -1 padded (0: a start cell off the grid);
+ *      path[B][nx*ny+1] with path_n[B] (both or neither): dkapath as Encode indices, start -> goal;
+ *      path_length[B]           dka.r.path_length (:112), a left fold over actualpath.
+ * Defined here where the reference fails or is silent:
+ *   - start cell == goal cell (the reference indexes nodes_collection[nothing], :93): found, one pop, a
+ *     one-cell path, length 0, cost 0;
+ *   - a start one cell off the grid is kept (Encode 0) and can step onto the grid; two cells off: one pop,
+ *     not found;
+ *   - a goal off the grid is never reached: the search exhausts the reachable cells, found = 0,
+ *     final_cost = 0.0. */
+int mp_dka_plan(mp_ctx* ctx, int32_t B, int32_t nx, int32_t ny, const double* bound, const double* start_real,
+                const double* goal_real, int32_t n_obs, const double* circles, double* final_cost, int32_t* found,
+                int32_t* pops, int32_t* n_nodes, int32_t* pop_seq, int32_t* path, int32_t* path_n,
+                double* path_length);
+
+/* planBFS! (PathPlanning/BreadthFirst/src/bfs_utils.jl:1-59 with FindNewNode :137-161) for B independent
+ * searches: the four axis moves (:140), a FIFO that is never sorted, a cell enters nodes_collection and the
+ * queue once.  One wavefront per search expands a whole level of the queue at a time and keeps the
+ * sequential loop's order: the pop sequence, the parents and the node count are the reference's, the nodes
+ * queued behind the goal in its level are not expanded.  Arguments, limits and the cases defined above as
+ * for mp_dka_plan, without final_cost (BFSNode carries no cost); pops never exceed nx*ny + 1.
+ *      path[B][nx*ny+1]   bfspath as Encode indices, start -> goal;
+ *      path_length[B]     an extension: BFSResult (BreadthFirst/src/types.jl:32-36) has no path_length; it
+ *                         is computed as planDKA! computes it, the same left fold over actualpath. */
+int mp_bfs_plan(mp_ctx* ctx, int32_t B, int32_t nx, int32_t ny, const double* bound, const double* start_real,
+                const double* goal_real, int32_t n_obs, const double* circles, int32_t* found, int32_t* pops,
+                int32_t* n_nodes, int32_t* pop_seq, int32_t* path, int32_t* path_n, double* path_length);
+
 /* ----------------------------------------------------------- RRT / RRT* */
 #define MP_RRT_MAX_ITER 1000000 /* cap on n_iter (the tree workspace is 48 bytes per node and scene) */
 

@@ -29,7 +29,7 @@ module MPGPU
 using Interpolations: interpolate, Gridded, Constant, Previous, linear_interpolation   # as the reference drivers
 
 export MPPIPlan, MPPIClosedLoop, planHybridAstar!, mppi_plan_batch, mppi_plan_sharded, comm_init, mppi_closed_loop_batch,
-       rollout_batch, ha_expand, ha_rs_connect, ha_astar_table, astar_plan_batch, rrt_plan_batch,
+       rollout_batch, ha_expand, ha_rs_connect, ha_astar_table, astar_plan_batch, dka_plan_batch, bfs_plan_batch, rrt_plan_batch,
        ha_allpath, ha_neighbor_origin, retrieve_batch!, track_batch!, ilqr_rollout, ilqr_backward!, ilqr_forward!,
        ilqr_solve!, vehicle_euler!, ctx_join
 
@@ -500,7 +500,58 @@ function astar_plan_batch(mapbound, bound::Matrix{Float64}, start_real::Matrix{F
             path_n = pn, path_length = plen)
 end
 
-struct RrtParams     # mp_rrt_params (PathPlanning/RRT/src/types.jl:19-39)
+"""
+    dka_plan_batch(mapbound, bound, start_real, goal_real, circles)
+
+planDKA! (PathPlanning/Dijkstra/src/dka_utils.jl:69-126) for B searches (mp_dka_plan): mapbound = (nx, ny),
+bound (4, B) = actualbound, start_real / goal_real (2, B), circles (3, n_obs, B) ([x, y, r]; pad a shorter list
+with [0, 0, 0]).  Returns final_cost, found, loop_count, n_nodes, the pop sequence (Encode indices, -1 padded),
+dkapath as Encode indices with its length per search, and path_length.
+"""
+function dka_plan_batch(mapbound, bound::Matrix{Float64}, start_real::Matrix{Float64}, goal_real::Matrix{Float64},
+                        circles::Array{Float64,3})
+    nx, ny = Int(mapbound[1]), Int(mapbound[2])
+    B = size(bound, 2); M = nx * ny + 1
+    n_obs = size(circles, 2)
+    cost = zeros(B); plen = zeros(B)
+    found = zeros(Int32, B); pops = zeros(Int32, B); nn = zeros(Int32, B); pn = zeros(Int32, B)
+    seq = zeros(Int32, 2M, B); path = zeros(Int32, M, B)
+    c = ctx()
+    check(GC.@preserve bound start_real goal_real circles cost plen found pops nn pn seq path ccall((:mp_dka_plan, libmpgpu), Cint,
+        (Ptr{Cvoid}, Int32, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64},
+         Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}),
+        c, B, nx, ny, bound, start_real, goal_real, n_obs, n_obs == 0 ? C_NULL : pointer(circles), cost, found, pops,
+        nn, seq, path, pn, plen), c)
+    return (; final_cost = cost, found, loop_count = pops, n_nodes = nn, pop_sequence = seq, dkapath = path,
+            path_n = pn, path_length = plen)
+end
+
+"""
+    bfs_plan_batch(mapbound, bound, start_real, goal_real, circles)
+
+planBFS! (PathPlanning/BreadthFirst/src/bfs_utils.jl:1-59) for B searches (mp_bfs_plan), arguments as for
+dka_plan_batch.  Returns found, loop_count, n_nodes, the pop sequence, bfspath as Encode indices with its length
+per search, and path_length (not a field of the reference's BFSResult: planDKA!'s fold over actualpath).
+"""
+function bfs_plan_batch(mapbound, bound::Matrix{Float64}, start_real::Matrix{Float64}, goal_real::Matrix{Float64},
+                        circles::Array{Float64,3})
+    nx, ny = Int(mapbound[1]), Int(mapbound[2])
+    B = size(bound, 2); M = nx * ny + 1
+    n_obs = size(circles, 2)
+    plen = zeros(B)
+    found = zeros(Int32, B); pops = zeros(Int32, B); nn = zeros(Int32, B); pn = zeros(Int32, B)
+    seq = zeros(Int32, 2M, B); path = zeros(Int32, M, B)
+    c = ctx()
+    check(GC.@preserve bound start_real goal_real circles plen found pops nn pn seq path ccall((:mp_bfs_plan, libmpgpu), Cint,
+        (Ptr{Cvoid}, Int32, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64},
+         Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}),
+        c, B, nx, ny, bound, start_real, goal_real, n_obs, n_obs == 0 ? C_NULL : pointer(circles), found, pops, nn,
+        seq, path, pn, plen), c)
+    return (; found, loop_count = pops, n_nodes = nn, pop_sequence = seq, bfspath = path, path_n = pn,
+            path_length = plen)
+end
+
+struct RrtParams    # mp_rrt_params (PathPlanning/RRT/src/types.jl:19-39)
     n_iter::Int32
     buffer_size::Int32
     rrt_star::Int32

@@ -199,6 +199,8 @@ SIGNATURES = {
     "mp_ha_plan_astar": (ctypes.c_int, [_V, ctypes.POINTER(HAParams), _I, _V, _V, _V, _I] + [_V] * 8),
     "mp_ha_astar_table": (ctypes.c_int, [_V, ctypes.POINTER(HAParams), _I, _V, _V, _V]),
     "mp_astar_plan": (ctypes.c_int, [_V, _I, _I, _I, _V, _V, _V, _I, _I] + [_V] * 9),
+    "mp_dka_plan": (ctypes.c_int, [_V, _I, _I, _I, _V, _V, _V, _I] + [_V] * 9),
+    "mp_bfs_plan": (ctypes.c_int, [_V, _I, _I, _I, _V, _V, _V, _I] + [_V] * 8),
     "mp_rrt_plan": (ctypes.c_int, [_V, ctypes.POINTER(RRTParams), _I, _V, _V, _V, _I] + [_V] * 13),
     "mp_ha_retrieve_path": (ctypes.c_int, [_V, _I, _V, _V, _V, _I] + [_V] * 8),
     "mp_ha_track": (ctypes.c_int, [_V, ctypes.POINTER(TrackParams), _I, _V, _V, _V, _I] + [_V] * 6 + [_I]),

@@ -1,13 +1,19 @@
-// astar.hip — the grid A* planner for gfx950 (PathPlanning/Astar/src/{setup,astar_utils}.jl,
-// CollisionDetection/src/utils.jl) + C-ABI: mp_astar_plan (B independent planAstar! searches) and
-// mp_ha_astar_table (Hybrid A*'s astar_heuristic, hybrid_astar_utils.jl:375-387, for every cell).
+// astar.hip — the grid planners for gfx950: A* (PathPlanning/Astar/src/{setup,astar_utils}.jl,
+// CollisionDetection/src/utils.jl), Dijkstra (PathPlanning/Dijkstra/src/dka_utils.jl) and breadth-first search
+// (PathPlanning/BreadthFirst/src/bfs_utils.jl) + C-ABI: mp_astar_plan, mp_dka_plan, mp_bfs_plan (B independent
+// planAstar! / planDKA! / planBFS! searches) and mp_ha_astar_table (Hybrid A*'s astar_heuristic,
+// hybrid_astar_utils.jl:375-387, for every cell).
 //
 // as_wall_kernel    Block2Pts: the 2x5 corner points of every block obstacle, once per scene.
 // as_mask_kernel    checkObsSafety for every cell of every scene, once per scene (one thread per cell):
 //                   a search only reads the scene's free-cell mask.
 // as_search_kernel  planAstar! + FindNewNode, one wavefront per search, the node table (Dict) and the
 //                   open list in LDS, no global hand-offs.  A scene's searches (one in plan mode, one per
-//                   start cell in table mode) share its mask.
+//                   start cell in table mode) share its mask.  as_search_kernel<true> is planDKA!: h = 0, so
+//                   f is g and one array holds both.
+// bfs_search_kernel planBFS! + FindNewNode, one wavefront per search, level by level: the FIFO never sorts
+//                   and a cell enters it once, so the queue is the pop sequence and a whole level expands
+//                   at once in the sequential loop's order.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -26,7 +32,11 @@ enum { ST_FREE = 1, ST_EXIST = 2, ST_OPEN = 4 };
 constexpr unsigned short AS_NOPAR = 0xFFFF;
 // LDS of one search, M = cells + 1 slots (slot 0: a start cell off the grid, Encode = 0): g, f and the
 // open list's sort keys (double), parent and two open-list buffers (uint16), the state bits (uint8)
-constexpr size_t as_lds_bytes(int M) { return (size_t)M * (3 * 8 + 3 * 2 + 1); }
+// (Dijkstra: f is g, two double arrays)
+constexpr size_t as_lds_bytes(int M, bool dka = false) { return (size_t)M * ((dka ? 2 : 3) * 8 + 3 * 2 + 1); }
+// ... of one breadth-first search: the claim word (uint32), parent and queue (uint16), the state bits (uint8)
+constexpr size_t bfs_lds_bytes(int M) { return (size_t)M * (4 + 2 * 2 + 1); }
+enum { AS_ASTAR = 0, AS_DKA = 1, AS_BFS = 2 };  // as_launch's planner
 
 // The reference's BLAS-dispatched products round as Julia's OpenBLAS does (oracle/or_blas.h), as in
 // hastar.hip: R*pts is dgemm with K = 2, transpose(pts .- bg_pt)*normal_vec is dgemv 'T' on two rows.
@@ -114,7 +124,7 @@ struct AsArgs {
   const int* scell;           // [searches][2] starting_pos (per_scene == 1)
   const int* gcell;           // [scenes][2] ending_pos
   const unsigned char* mask;  // [scenes][nx*ny]
-  double* cost;               // [searches] final_cost
+  double* cost;               // [searches] final_cost (null: breadth-first search has none)
   int *found, *pops, *n_nodes;  // [searches] (each may be null)
   int* pop_seq;               // [searches][cap] Encode index per pop, or null
   int* path;                  // [searches][nx*ny + 1] astarpath as Encode indices, start -> goal, or null
@@ -128,13 +138,38 @@ struct AsArgs {
 __device__ const signed char AS_DX[9] = {-1, -1, -1, 1, 1, 1, 0, 1, 0};
 __device__ const signed char AS_DY[9] = {0, -1, -1, -1, 0, 1, -1, -1, 1};
 
+// sum(norm(actualpath[i+1, :] - actualpath[i, :])) (astar_utils.jl:129, dka_utils.jl:112), a left fold over
+// the path's cnt cells, held goal side first in rev
+template <typename T>
+__device__ __forceinline__ double as_path_length(const T* rev, int cnt, int nx, int sx, int sy, double xf, double yf,
+                                                 const double* ge) {
+  double acc = 0.0;
+  double ax = 0.0, ay = 0.0;
+  for (int i = 0; i < cnt; i++) {
+    const int c = rev[cnt - 1 - i];
+    const int px = c == 0 ? sx : (c - 1) % nx + 1, py = c == 0 ? sy : (c - 1) / nx + 1;
+    const double tx = ((double)px - 1.0) * xf + ge[0], ty = ((double)py - 1.0) * yf + ge[1];
+    if (i > 0) {
+      const double ex = tx - ax, ey = ty - ay;
+      const double n = mpj_sqrt(ex * ex + ey * ey);
+      acc = i == 1 ? n : acc + n;
+    }
+    ax = tx;
+    ay = ty;
+  }
+  return acc;
+}
+
+// DKA: planDKA! (dka_utils.jl:69-126, FindNewNode :175-215) -- the same directions, sort and InOpen rule with
+// no temp_h: f = g + 0.0 = g exactly, so f aliases g and the update test reads f (:193)
+template <bool DKA>
 __global__ __launch_bounds__(64) void as_search_kernel(AsArgs A) {
   extern __shared__ double as_sm[];
   __shared__ int s_cur;
   const int nx = A.nx, ny = A.ny, N = nx * ny, M = N + 1;
   const int lane = threadIdx.x, q = blockIdx.x, scene = q / A.per_scene;
   double* g = as_sm;
-  double* f = g + M;
+  double* f = DKA ? g : g + M;
   double* kf = f + M;
   unsigned short* par = reinterpret_cast<unsigned short*>(kf + M);
   unsigned short* cur_o = par + M;
@@ -223,19 +258,22 @@ __global__ __launch_bounds__(64) void as_search_kernel(AsArgs A) {
         const unsigned char sv = st[ncell];
         if (sv & ST_FREE) {
           const double tg = gc + mpj_sqrt((double)(dx * dx) * xf2 + (double)(dy * dy) * yf2);
-          const int hx = px - gx, hy = py - gy;
-          const double th = mpj_sqrt((double)((long long)hx * hx) * xf2 + (double)((long long)hy * hy) * yf2);
-          const double tf = tg + th;
+          double tf = tg;
+          if constexpr (!DKA) {
+            const int hx = px - gx, hy = py - gy;
+            const double th = mpj_sqrt((double)((long long)hx * hx) * xf2 + (double)((long long)hy * hy) * yf2);
+            tf = tg + th;
+          }
           bool upd = false;
           if (sv & ST_EXIST) {
-            upd = tg < g[ncell];
+            upd = DKA ? tf < f[ncell] : tg < g[ncell];
           } else {
             upd = true;
             isnew = true;
           }
           if (upd) {
             g[ncell] = tg;
-            f[ncell] = tf;
+            if constexpr (!DKA) f[ncell] = tf;
             par[ncell] = (unsigned short)cur;
             app = !(sv & ST_OPEN);  // InOpen (:145-152)
             st[ncell] = sv | ST_EXIST | ST_OPEN;
@@ -267,23 +305,115 @@ __global__ __launch_bounds__(64) void as_search_kernel(AsArgs A) {
     if (A.n_nodes) A.n_nodes[q] = nn;
     if (A.path_n) A.path_n[q] = cnt;
     if (capped) *A.err = 1;
-    if (A.path_len) {  // sum(norm(actualpath[i+1, :] - actualpath[i, :])) (:129), a left fold
-      double acc = 0.0;
-      double ax = 0.0, ay = 0.0;
-      for (int i = 0; i < cnt; i++) {
-        const int c = nxt_o[cnt - 1 - i];
-        const int px = c == 0 ? sx : (c - 1) % nx + 1, py = c == 0 ? sy : (c - 1) / nx + 1;
-        const double tx = ((double)px - 1.0) * xf + ge[0], ty = ((double)py - 1.0) * yf + ge[1];
-        if (i > 0) {
-          const double ex = tx - ax, ey = ty - ay;
-          const double n = mpj_sqrt(ex * ex + ey * ey);
-          acc = i == 1 ? n : acc + n;
-        }
-        ax = tx;
-        ay = ty;
-      }
-      A.path_len[q] = acc;
+    if (A.path_len) A.path_len[q] = as_path_length(nxt_o, cnt, nx, sx, sy, xf, yf, ge);
+  }
+}
+
+// FindNewNode's directions (bfs_utils.jl:140)
+__device__ const signed char BFS_DX[4] = {-1, 1, 0, 0};
+__device__ const signed char BFS_DY[4] = {0, 0, -1, 1};
+
+// planBFS! (bfs_utils.jl:1-59) + FindNewNode (:137-161).  popfirst! on a list that is only ever push!-ed to, and
+// haskey keeps a cell from entering twice: queue position i is pop i + 1, and a level (the nodes one hop
+// further than the last) is a run of positions [h, tail).  Candidate c = 4*i + d is direction d of the node
+// at position i; the sequential loop gives a new cell to the lowest candidate that reaches it, and appends
+// the winners in candidate order.
+__global__ __launch_bounds__(64) void bfs_search_kernel(AsArgs A) {
+  extern __shared__ unsigned int bfs_sm[];
+  __shared__ int s_goal, s_cnt;
+  const int nx = A.nx, ny = A.ny, N = nx * ny, M = N + 1;
+  const int lane = threadIdx.x, q = blockIdx.x;
+  unsigned int* claim = bfs_sm;
+  unsigned short* par = reinterpret_cast<unsigned short*>(claim + M);
+  unsigned short* que = par + M;
+  unsigned char* st = reinterpret_cast<unsigned char*>(que + M);
+  const double* ge = A.geo + (size_t)q * 4;
+  const int sx = A.scell[2 * q], sy = A.scell[2 * q + 1];
+  const int gx = A.gcell[2 * q], gy = A.gcell[2 * q + 1];
+  const unsigned char* mk = A.mask + (size_t)q * N;
+  for (int i = lane; i < M; i += 64) {
+    st[i] = (i > 0 && mk[i - 1]) ? ST_FREE : 0;
+    claim[i] = 0xFFFFFFFFu;
+  }
+  __syncthreads();
+  // Encode (bfs_utils.jl:123-135); a goal off the grid matches no cell a search can enter
+  const int s_enc = (sx < 1 || sx > nx || sy < 1 || sy > ny) ? 0 : (sy - 1) * nx + sx;
+  const int g_enc = (gx < 1 || gx > nx || gy < 1 || gy > ny) ? 0 : (gy - 1) * nx + gx;
+  if (lane == 0) {  // starting_node (setup.jl:20-21), pushed at :3
+    par[s_enc] = AS_NOPAR;
+    st[s_enc] |= ST_EXIST;
+    que[0] = (unsigned short)s_enc;
+    s_goal = (sx == gx && sy == gy) ? 0 : -1;  // (start == goal: found at the first pop -- :25 throws)
+  }
+  __syncthreads();
+  // the neighbour cell of candidate c (0: off the grid) and the cell it is reached from
+  auto neighbour = [&](int c, int& cell) {
+    cell = que[c >> 2];
+    const int cx = cell == 0 ? sx : (cell - 1) % nx + 1, cy = cell == 0 ? sy : (cell - 1) / nx + 1;
+    const int px = cx + BFS_DX[c & 3], py = cy + BFS_DY[c & 3];
+    return (px >= 1 && px <= nx && py >= 1 && py <= ny) ? (py - 1) * nx + px : 0;  // checkPositionValidity (:169-176)
+  };
+  int h = 0, tail = 1, found = 0;
+  int gpos = s_goal;  // the goal's queue position, known from the moment it is appended
+  while (h < tail) {
+    const int lvl_end = tail;
+    int n_exp = lvl_end - h;
+    if (gpos >= 0) {  // the goal is in this level: only the nodes ahead of it were popped before it (:23)
+      found = 1;
+      n_exp = gpos - h;
     }
+    const int c0 = 4 * h, c1 = 4 * (h + n_exp);
+    for (int c = c0 + lane; c < c1; c += 64) {
+      int cell;
+      const int nb = neighbour(c, cell);
+      if (nb > 0 && (st[nb] & (ST_FREE | ST_EXIST)) == ST_FREE) atomicMin(&claim[nb], (unsigned int)c);  // (:147,:152)
+    }
+    __syncthreads();
+    // a candidate is unique to its (position, direction), so claim[nb] == c only for this level's winner
+    for (int base = c0; base < c1; base += 64) {
+      const int c = base + lane;
+      int cell = 0, nb = 0;
+      bool win = false;
+      if (c < c1) {
+        nb = neighbour(c, cell);
+        win = nb > 0 && claim[nb] == (unsigned int)c;
+      }
+      const unsigned long long wm = __ballot(win);
+      if (win) {  // :153-155
+        const int slot = tail + __popcll(wm & ((1ull << lane) - 1));
+        par[nb] = (unsigned short)cell;
+        st[nb] |= ST_EXIST;
+        que[slot] = (unsigned short)nb;
+        if (nb == g_enc) s_goal = slot;
+      }
+      tail += __popcll(wm);
+    }
+    __syncthreads();
+    if (found) break;
+    gpos = s_goal;
+    h = lvl_end;
+  }
+  // every queued node is in nodes_collection; the pops are the queue up to the goal, or all of it
+  const int pops = found ? gpos + 1 : tail;
+  if (A.pop_seq)
+    for (int i = lane; i < pops; i += 64) A.pop_seq[(size_t)q * A.cap + i] = que[i];
+  // bfspath (:24-35) by the parent chain, goal side first into the claim words (the search is over)
+  if (lane == 0) {
+    int cnt = 0;
+    if (found)
+      for (int c = que[gpos]; c != AS_NOPAR && cnt < M; c = par[c]) claim[cnt++] = (unsigned int)c;
+    s_cnt = cnt;
+  }
+  __syncthreads();
+  const int cnt = s_cnt;
+  if (A.path)
+    for (int i = lane; i < cnt; i += 64) A.path[(size_t)q * M + i] = (int)claim[cnt - 1 - i];
+  if (lane == 0) {
+    if (A.found) A.found[q] = found;
+    if (A.pops) A.pops[q] = pops;
+    if (A.n_nodes) A.n_nodes[q] = tail;
+    if (A.path_n) A.path_n[q] = cnt;
+    if (A.path_len) A.path_len[q] = as_path_length(claim, cnt, nx, sx, sy, ge[2], ge[3], ge);
   }
 }
 
@@ -305,14 +435,14 @@ bool as_cell(const double* ge, const double* real, int* cell) {
 }
 
 // masks + searches on the context stream (no synchronisation).  obs_dev: [scenes][n_obs][kind] on the device.
-int as_launch(mp_ctx* ctx, int scenes, int kind, int n_obs, const double* obs_dev, AsArgs A) {
+int as_launch(mp_ctx* ctx, int planner, int scenes, int kind, int n_obs, const double* obs_dev, AsArgs A) {
   const int N = A.nx * A.ny;
   unsigned char* mask = (unsigned char*)mp_ws(ctx, WS_AS_MASK, (size_t)scenes * N);
   int* err = (int*)mp_ws(ctx, WS_AS_ERR, sizeof(int));
   if (!mask || !err) return MP_ERR_NOMEM;
   MP_HIP(ctx, hipMemsetAsync(err, 0, sizeof(int), ctx->stream));
   const double* wpts = nullptr;
-  if (n_obs == 0) {  // an empty obstacle list (the reference indexes obstacle_list[1]): all free
+  if (n_obs == 0) {  // an empty obstacle list (A* indexes obstacle_list[1]; Dijkstra and BFS loop over 1:0): all free
     MP_HIP(ctx, hipMemsetAsync(mask, 1, (size_t)scenes * N, ctx->stream));
   } else {
     if (kind == 5) {
@@ -330,13 +460,27 @@ int as_launch(mp_ctx* ctx, int scenes, int kind, int n_obs, const double* obs_de
   A.mask = mask;
   A.err = err;
   A.cap = 2 * (N + 1);
-  const size_t lds = as_lds_bytes(N + 1);
-  if (lds > 48 * 1024 && !ctx->astar_lds_attr) {
-    MP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(as_search_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)as_lds_bytes(AS_MAX_CELLS + 1)));
-    ctx->astar_lds_attr = true;
+  const dim3 grid((unsigned)(scenes * A.per_scene));
+  if (planner == AS_BFS) {  // 23.4 KB at the largest grid: no attribute to raise
+    hipLaunchKernelGGL(bfs_search_kernel, grid, dim3(64), bfs_lds_bytes(N + 1), ctx->stream, A);
+  } else if (planner == AS_DKA) {  // (the attribute is per kernel function: each instance has its own flag)
+    const size_t lds = as_lds_bytes(N + 1, true);
+    if (lds > 48 * 1024 && !ctx->dka_lds_attr) {
+      MP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(as_search_kernel<true>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)as_lds_bytes(AS_MAX_CELLS + 1, true)));
+      ctx->dka_lds_attr = true;
+    }
+    hipLaunchKernelGGL(as_search_kernel<true>, grid, dim3(64), lds, ctx->stream, A);
+  } else {
+    const size_t lds = as_lds_bytes(N + 1);
+    if (lds > 48 * 1024 && !ctx->astar_lds_attr) {
+      MP_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(as_search_kernel<false>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)as_lds_bytes(AS_MAX_CELLS + 1)));
+      ctx->astar_lds_attr = true;
+    }
+    hipLaunchKernelGGL(as_search_kernel<false>, grid, dim3(64), lds, ctx->stream, A);
   }
-  hipLaunchKernelGGL(as_search_kernel, dim3((unsigned)(scenes * A.per_scene)), dim3(64), lds, ctx->stream, A);
   MP_HIP(ctx, hipGetLastError());
   return MP_OK;
 }
@@ -345,8 +489,65 @@ int as_check_err(mp_ctx* ctx) {
   int err = 0;
   MP_HIP(ctx, hipMemcpyAsync(&err, mp_ws(ctx, WS_AS_ERR, sizeof(int)), sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   MP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (err) return mp_fail(ctx, MP_ERR_NUMERIC, "grid A*: a search reached its pop cap (2 * (nx*ny + 1))");
+  if (err) return mp_fail(ctx, MP_ERR_NUMERIC, "grid search: a search reached its pop cap (2 * (nx*ny + 1))");
   return MP_OK;
+}
+
+// the body of mp_astar_plan / mp_dka_plan / mp_bfs_plan behind their argument checks (final_cost: null for BFS)
+int as_plan(mp_ctx* ctx, int planner, int B, int nx, int ny, const double* bound, const double* start_real,
+            const double* goal_real, int obs_kind, int n_obs, const double* obstacles, double* final_cost, int32_t* found,
+            int32_t* pops, int32_t* n_nodes, int32_t* pop_seq, int32_t* path, int32_t* path_n, double* path_length) {
+  MP_CHECK(ctx, nx >= 2 && ny >= 2 && (long long)nx * ny <= AS_MAX_CELLS,
+           "grid %d x %d: each side must be >= 2 and nx*ny <= %d", nx, ny, AS_MAX_CELLS);
+  MP_CHECK(ctx, obs_kind == 3 || obs_kind == 5, "obstacle kind must be 3 (circles) or 5 (blocks)");
+  MP_CHECK(ctx, n_obs >= 0 && (n_obs == 0 || obstacles), "bad obstacle list");
+  MP_CHECK(ctx, (path != nullptr) == (path_n != nullptr), "the path and path_n go together");
+  MP_HIP(ctx, hipSetDevice(ctx->device));
+  const int N = nx * ny, M = N + 1, cap = 2 * M;
+  const size_t nB = (size_t)B;
+  std::vector<double> ge(4 * nB);
+  std::vector<int> sc(2 * nB), gc(2 * nB);
+  for (int s = 0; s < B; s++) {
+    MP_CHECK(ctx, as_factors(bound + 4 * (size_t)s, nx, ny, &ge[4 * s]), "bound %d must be finite", s);
+    MP_CHECK(ctx, as_cell(&ge[4 * s], start_real + 2 * (size_t)s, &sc[2 * s]) &&
+                      as_cell(&ge[4 * s], goal_real + 2 * (size_t)s, &gc[2 * s]),
+             "search %d: a start or goal cell is not an integer", s);
+  }
+  int st = MP_OK;
+  AsArgs A{};
+  A.nx = nx;
+  A.ny = ny;
+  A.per_scene = 1;
+  A.geo = mp_upload(ctx, WS_AS_GEO, ge.data(), ge.size(), &st);
+  A.gcell = mp_upload(ctx, WS_AS_GCELL, gc.data(), gc.size(), &st);
+  A.scell = mp_upload(ctx, WS_AS_SCELL, sc.data(), sc.size(), &st);
+  const double* dobs = n_obs ? mp_upload(ctx, WS_AS_OBS, obstacles, nB * n_obs * obs_kind, &st) : nullptr;
+  // outputs: [cost B doubles | path_len B doubles | found, pops, n_nodes, path_n B ints each | pop_seq | path]
+  char* out = (char*)mp_ws(ctx, WS_AS_TABLE, nB * (16 + 16 + 4 * ((size_t)cap + M)));
+  if (st || !A.geo || !A.gcell || !A.scell || (n_obs && !dobs) || !out) return st ? st : MP_ERR_NOMEM;
+  double* dcost = (double*)out;
+  A.cost = planner == AS_BFS ? nullptr : dcost;
+  A.path_len = dcost + nB;
+  A.found = (int*)(A.path_len + nB);
+  A.pops = A.found + nB;
+  A.n_nodes = A.pops + nB;
+  A.path_n = A.n_nodes + nB;
+  int* dseq = A.path_n + nB;
+  int* dpath = dseq + nB * cap;
+  A.pop_seq = pop_seq ? dseq : nullptr;
+  A.path = path ? dpath : nullptr;
+  if (pop_seq) MP_HIP(ctx, hipMemsetAsync(dseq, 0xff, sizeof(int) * nB * cap, ctx->stream));  // -1 past the pops
+  if (path) MP_HIP(ctx, hipMemsetAsync(dpath, 0xff, sizeof(int) * nB * M, ctx->stream));
+  if ((st = as_launch(ctx, planner, B, obs_kind, n_obs, dobs, A))) return st;
+  if ((st = mp_download(ctx, final_cost, (const double*)A.cost, nB))) return st;
+  if ((st = mp_download(ctx, path_length, (const double*)A.path_len, nB))) return st;
+  if ((st = mp_download(ctx, found, (const int32_t*)A.found, nB))) return st;
+  if ((st = mp_download(ctx, pops, (const int32_t*)A.pops, nB))) return st;
+  if ((st = mp_download(ctx, n_nodes, (const int32_t*)A.n_nodes, nB))) return st;
+  if ((st = mp_download(ctx, path_n, (const int32_t*)A.path_n, nB))) return st;
+  if ((st = mp_download(ctx, pop_seq, (const int32_t*)dseq, nB * cap))) return st;
+  if ((st = mp_download(ctx, path, (const int32_t*)dpath, nB * M))) return st;
+  return as_check_err(ctx);
 }
 
 }  // namespace
@@ -375,7 +576,7 @@ int mp_as_table_dev(mp_ctx* ctx, const mp_ha_params* p, int B, const double* goa
   double* tab = (double*)mp_ws(ctx, WS_AS_TABLE, sizeof(double) * N * (size_t)B);
   if (st || !A.geo || !A.gcell || !tab) return st ? st : MP_ERR_NOMEM;
   A.cost = tab;
-  if ((st = as_launch(ctx, B, 5, p->n_walls, walls_dev, A))) return st;
+  if ((st = as_launch(ctx, AS_ASTAR, B, 5, p->n_walls, walls_dev, A))) return st;
   *table_dev = tab;
   return MP_OK;
 }
@@ -389,56 +590,26 @@ int mp_astar_plan(mp_ctx* ctx, int32_t B, int32_t nx, int32_t ny, const double* 
                   int32_t* astarpath, int32_t* path_n, double* path_length) {
   if (!ctx) return MP_ERR_INVALID;
   MP_CHECK(ctx, B >= 1 && bound && start_real && goal_real && final_cost && found && pops && n_nodes, "bad arguments");
-  MP_CHECK(ctx, nx >= 2 && ny >= 2 && (long long)nx * ny <= AS_MAX_CELLS,
-           "grid %d x %d: each side must be >= 2 and nx*ny <= %d", nx, ny, AS_MAX_CELLS);
-  MP_CHECK(ctx, obs_kind == 3 || obs_kind == 5, "obstacle kind must be 3 (circles) or 5 (blocks)");
-  MP_CHECK(ctx, n_obs >= 0 && (n_obs == 0 || obstacles), "bad obstacle list");
-  MP_CHECK(ctx, (astarpath != nullptr) == (path_n != nullptr), "astarpath and path_n go together");
-  MP_HIP(ctx, hipSetDevice(ctx->device));
-  const int N = nx * ny, M = N + 1, cap = 2 * M;
-  const size_t nB = (size_t)B;
-  std::vector<double> ge(4 * nB);
-  std::vector<int> sc(2 * nB), gc(2 * nB);
-  for (int s = 0; s < B; s++) {
-    MP_CHECK(ctx, as_factors(bound + 4 * (size_t)s, nx, ny, &ge[4 * s]), "bound %d must be finite", s);
-    MP_CHECK(ctx, as_cell(&ge[4 * s], start_real + 2 * (size_t)s, &sc[2 * s]) &&
-                      as_cell(&ge[4 * s], goal_real + 2 * (size_t)s, &gc[2 * s]),
-             "search %d: a start or goal cell is not an integer", s);
-  }
-  int st = MP_OK;
-  AsArgs A{};
-  A.nx = nx;
-  A.ny = ny;
-  A.per_scene = 1;
-  A.geo = mp_upload(ctx, WS_AS_GEO, ge.data(), ge.size(), &st);
-  A.gcell = mp_upload(ctx, WS_AS_GCELL, gc.data(), gc.size(), &st);
-  A.scell = mp_upload(ctx, WS_AS_SCELL, sc.data(), sc.size(), &st);
-  const double* dobs = n_obs ? mp_upload(ctx, WS_AS_OBS, obstacles, nB * n_obs * obs_kind, &st) : nullptr;
-  // outputs: [cost B doubles | path_len B doubles | found, pops, n_nodes, path_n B ints each | pop_seq | path]
-  char* out = (char*)mp_ws(ctx, WS_AS_TABLE, nB * (16 + 16 + 4 * ((size_t)cap + M)));
-  if (st || !A.geo || !A.gcell || !A.scell || (n_obs && !dobs) || !out) return st ? st : MP_ERR_NOMEM;
-  A.cost = (double*)out;
-  A.path_len = A.cost + nB;
-  A.found = (int*)(A.path_len + nB);
-  A.pops = A.found + nB;
-  A.n_nodes = A.pops + nB;
-  A.path_n = A.n_nodes + nB;
-  int* dseq = A.path_n + nB;
-  int* dpath = dseq + nB * cap;
-  A.pop_seq = pop_seq ? dseq : nullptr;
-  A.path = astarpath ? dpath : nullptr;
-  if (pop_seq) MP_HIP(ctx, hipMemsetAsync(dseq, 0xff, sizeof(int) * nB * cap, ctx->stream));  // -1 past the pops
-  if (astarpath) MP_HIP(ctx, hipMemsetAsync(dpath, 0xff, sizeof(int) * nB * M, ctx->stream));
-  if ((st = as_launch(ctx, B, obs_kind, n_obs, dobs, A))) return st;
-  if ((st = mp_download(ctx, final_cost, (const double*)A.cost, nB))) return st;
-  if ((st = mp_download(ctx, path_length, (const double*)A.path_len, nB))) return st;
-  if ((st = mp_download(ctx, found, (const int32_t*)A.found, nB))) return st;
-  if ((st = mp_download(ctx, pops, (const int32_t*)A.pops, nB))) return st;
-  if ((st = mp_download(ctx, n_nodes, (const int32_t*)A.n_nodes, nB))) return st;
-  if ((st = mp_download(ctx, path_n, (const int32_t*)A.path_n, nB))) return st;
-  if ((st = mp_download(ctx, pop_seq, (const int32_t*)dseq, nB * cap))) return st;
-  if ((st = mp_download(ctx, astarpath, (const int32_t*)dpath, nB * M))) return st;
-  return as_check_err(ctx);
+  return as_plan(ctx, AS_ASTAR, B, nx, ny, bound, start_real, goal_real, obs_kind, n_obs, obstacles, final_cost, found,
+                 pops, n_nodes, pop_seq, astarpath, path_n, path_length);
+}
+
+int mp_dka_plan(mp_ctx* ctx, int32_t B, int32_t nx, int32_t ny, const double* bound, const double* start_real,
+                const double* goal_real, int32_t n_obs, const double* circles, double* final_cost, int32_t* found,
+                int32_t* pops, int32_t* n_nodes, int32_t* pop_seq, int32_t* path, int32_t* path_n, double* path_length) {
+  if (!ctx) return MP_ERR_INVALID;
+  MP_CHECK(ctx, B >= 1 && bound && start_real && goal_real && final_cost && found && pops && n_nodes, "bad arguments");
+  return as_plan(ctx, AS_DKA, B, nx, ny, bound, start_real, goal_real, 3, n_obs, circles, final_cost, found, pops,
+                 n_nodes, pop_seq, path, path_n, path_length);
+}
+
+int mp_bfs_plan(mp_ctx* ctx, int32_t B, int32_t nx, int32_t ny, const double* bound, const double* start_real,
+                const double* goal_real, int32_t n_obs, const double* circles, int32_t* found, int32_t* pops,
+                int32_t* n_nodes, int32_t* pop_seq, int32_t* path, int32_t* path_n, double* path_length) {
+  if (!ctx) return MP_ERR_INVALID;
+  MP_CHECK(ctx, B >= 1 && bound && start_real && goal_real && found && pops && n_nodes, "bad arguments");
+  return as_plan(ctx, AS_BFS, B, nx, ny, bound, start_real, goal_real, 3, n_obs, circles, nullptr, found, pops, n_nodes,
+                 pop_seq, path, path_n, path_length);
 }
 
 int mp_ha_astar_table(mp_ctx* ctx, const mp_ha_params* p, int32_t B, const double* goal, const double* walls,

@@ -57,7 +57,8 @@ struct mp_ctx {
   // (a context is used by one thread at a time, so the flags need no lock)
   bool mppi_lds_attr = false, fin_lds_attr = false;
   bool ilqr_fused_attr = false;  // the fused iLQR backward kernel's dynamic-LDS attribute is set
-  bool astar_lds_attr = false;  // as_search_kernel's dynamic-LDS attribute is set
+  bool astar_lds_attr = false;  // as_search_kernel<false>'s dynamic-LDS attribute is set
+  bool dka_lds_attr = false;    // ... and the Dijkstra instance's (the attribute is per kernel function)
   // host copies of the grid A* table's per-scene geometry (they outlive the asynchronous uploads)
   std::vector<double> as_geo_host;
   std::vector<int> as_gcell_host;
