@@ -193,8 +193,14 @@ __device__ __forceinline__ T ld_ag(const T* p) {
 // INL: device Philox noise drawn inside the rollout loop (else the caller's noise, transposed
 // by noise_prep_kernel): a compile-time mode, so the rollout loop carries neither the other
 // mode's registers nor its branch (measured 318 -> 306 us per 8-scene launch, 224 -> 212 us single scene).
-template <int BT, int LPR, bool INL>
+// LEAN: the instance for the common collecting call (plan_launch picks it), with the optional features
+// fixed at compile time -- no circle obstacles, the occupancy grid staged in LDS, the control cost on
+// with its rows in LDS, both collection outputs present, no LDS control lists, device noise, K < 2^27 --
+// so the rollout loop carries none of their run-time tests (a null test of a per-lane pointer is an exec
+// mask), and the collection stores go from a wave-uniform base with a fixed 32-bit lane offset.
+template <int BT, int LPR, bool INL, bool LEAN = false>
 __global__ __launch_bounds__(BT) void mppi_plan_kernel(MppiDev P, PlanArgs A) {
+  static_assert(!LEAN || (INL && LPR == 1), "lean instance: device noise, one rollout per lane");
   constexpr int NT = BT, RPB = BT / LPR, NQ = BT / 128;
   // WPART: the block partial Σ e·u is formed per wave over the wave's own 32 rollouts (lane pair
   // layout, H <= 64), with the HBM control lists prefetched into registers as soon as the wave's
@@ -227,24 +233,24 @@ __global__ __launch_bounds__(BT) void mppi_plan_kernel(MppiDev P, PlanArgs A) {
   // global loads but the prefetched noise, so no s_waitcnt vmcnt ever waits on
   // the (uncoalesced) TrajectoryCollection stores (CDNA4 vmcnt counts stores).
   double* unom = dyn + A.lds_unom;
-  double* obs = A.obs ? dyn + A.lds_obs : nullptr;
-  double* ush = A.lds_ctrl >= 0 ? dyn + A.lds_ctrl : nullptr;  // [RPB][H2+1] this block's control lists
+  double* obs = !LEAN && A.obs ? dyn + A.lds_obs : nullptr;
+  double* ush = !LEAN && A.lds_ctrl >= 0 ? dyn + A.lds_ctrl : nullptr;  // [RPB][H2+1] this block's control lists
   const int ustr = H2 + 1;
   const unsigned char* grid = nullptr;
   {
     const double* gu = A.unom + (size_t)H2 * s;
     rollout_tab_fill(atab, P, tid, NT);
     for (int i = tid; i < H2; i += NT) unom[i] = gu[i];
-    if (P.ctrl_cost)
+    if (LEAN || P.ctrl_cost)
       for (int i = tid; i < H; i += NT) ctrl_cost_row(P, gu[2 * i], gu[2 * i + 1], dyn + A.lds_cq + 2 * i);
-    if (A.obs) {
+    if (!LEAN && A.obs) {
       const double* go = A.obs + (size_t)3 * P.n_obs * s;
       for (int i = tid; i < 3 * P.n_obs; i += NT) obs[i] = go[i];
     }
-    if (A.grid) {
+    if (LEAN || A.grid) {
       const int gb = P.gnx * P.gny;
       const unsigned char* gg = A.grid + (size_t)gb * s;
-      if (A.lds_grid >= 0) {
+      if (LEAN || A.lds_grid >= 0) {
         unsigned char* lg = reinterpret_cast<unsigned char*>(dyn + A.lds_grid);
         for (int i = tid; i < gb; i += NT) lg[i] = gg[i];
         grid = lg;
@@ -255,6 +261,14 @@ __global__ __launch_bounds__(BT) void mppi_plan_kernel(MppiDev P, PlanArgs A) {
     __syncthreads();
   }
   double* ctrl_g = A.ctrl_all ? A.ctrl_all + ((size_t)s * H * K + kk) * 2 + side : nullptr;  // LPR 1: + 0
+  // LEAN: the same addresses as a wave-uniform base (moved by one step's row, 16 K bytes, per step on the
+  // scalar unit) plus the lane's fixed byte offset; likewise the states (TrajUni)
+  unsigned long long ctrl_u = LEAN ? reinterpret_cast<unsigned long long>(A.ctrl_all + (size_t)s * H * K * 2) : 0;
+  unsigned ctrl_off = (unsigned)kk * 16u;
+  const unsigned ctrl_row = (unsigned)K * 16u;
+  // LEAN: the steps at which the no-sibling path below changes priority, (4j) % H < 4 with q = (4j) / H
+  // = 1, 2, 3, are j = ceil(qH / 4): one j per q, since [qH, qH + 4) holds one multiple of 4
+  const int pq1 = (H + 3) >> 2, pq2 = (2 * H + 3) >> 2, pq3 = (3 * H + 3) >> 2;
 
 #if MPPI_PRIO == 3
   // Sibling-paced issue priority: each wave publishes its step in LDS and finds the other wave of the
@@ -329,8 +343,20 @@ __global__ __launch_bounds__(BT) void mppi_plan_kernel(MppiDev P, PlanArgs A) {
         if (j > o) __builtin_amdgcn_s_setprio(0);
         else if (j < o) __builtin_amdgcn_s_setprio(2);
         else __builtin_amdgcn_s_setprio(1);
-        sh_prog[wv] = j;
-        sib_j = sh_prog[sib];
+        if (LEAN) {
+          // the same two volatile accesses through an LDS pointer: reached through the lambda's reference they
+          // are flat ones, whose vmcnt(0) waits also wait for the step's TrajectoryCollection stores
+          typedef __attribute__((address_space(3))) volatile int* lds_vip;
+          ((lds_vip)sh_prog)[wv] = j;
+          sib_j = ((lds_vip)sh_prog)[sib];
+        } else {
+          sh_prog[wv] = j;
+          sib_j = sh_prog[sib];
+        }
+      } else if (LEAN) {  // the quarter levels below without the per-step division (where two coincide, the later)
+        if (j == pq3) __builtin_amdgcn_s_setprio(0);
+        else if (j == pq2) __builtin_amdgcn_s_setprio(1);
+        else if (j == pq1) __builtin_amdgcn_s_setprio(2);
       } else if ((4 * j) % H < 4 && j > 0) {  // no sibling in the block on this SIMD: quarter levels
         const int q = (4 * j) / H;
         if (q == 1) __builtin_amdgcn_s_setprio(2);
@@ -350,7 +376,11 @@ __global__ __launch_bounds__(BT) void mppi_plan_kernel(MppiDev P, PlanArgs A) {
 #endif
     };
     auto store = [&](int j, const double* u) {
-      if (LPR == 2) {
+      if (LEAN) {
+        typedef double d2v __attribute__((ext_vector_type(2)));  // one 16-byte store, as the double2's
+        *reinterpret_cast<__attribute__((address_space(1))) d2v*>(uni_addr(ctrl_u, ctrl_off)) = d2v{u[0], u[1]};
+        ctrl_u += ctrl_row;
+      } else if (LPR == 2) {
         if (ush) ush[pair * ustr + 2 * j + side] = u[side];
         if (ctrl_g) {
 #if MPPI_NT_CTRL
@@ -368,8 +398,14 @@ __global__ __launch_bounds__(BT) void mppi_plan_kernel(MppiDev P, PlanArgs A) {
       }
     };
     // inactive pairs (k >= K) recompute rollout K-1 and write identical values
-    const TrajOut traj{A.coll_traj ? A.coll_traj + (size_t)s * (H + 1) * 7 * K + kk : nullptr, 7LL * K, (long long)K};
-    c = rollout_pair<LPR>(P, X0, goal, obs, grid, unom, side, ctrl, store, traj, &feas, atab, dyn + A.lds_cq);
+    if constexpr (LEAN) {
+      const TrajUni traj{reinterpret_cast<unsigned long long>(A.coll_traj + (size_t)s * (H + 1) * 7 * K), (unsigned)kk * 8u,
+                         (unsigned)K * 8u};
+      c = rollout_pair<LPR, true>(P, X0, goal, obs, grid, unom, side, ctrl, store, traj, &feas, atab, dyn + A.lds_cq);
+    } else {
+      const TrajOut traj{A.coll_traj ? A.coll_traj + (size_t)s * (H + 1) * 7 * K + kk : nullptr, 7LL * K, (long long)K};
+      c = rollout_pair<LPR>(P, X0, goal, obs, grid, unom, side, ctrl, store, traj, &feas, atab, dyn + A.lds_cq);
+    }
   }
   MP_STAMP(1);
   MP_STAMP_WAVE();
@@ -912,7 +948,12 @@ static int make_dev_params(mp_ctx* ctx, const mp_mppi_params* p, int K, MppiDev*
 
 // the plan kernel instance for a block size, lanes per rollout and noise source
 using PlanFn = void (*)(MppiDev, PlanArgs);
-static PlanFn plan_kernel_for(int BT, int LPR, bool inl) {
+static PlanFn plan_kernel_for(int BT, int LPR, bool inl, bool lean = false) {
+  if (lean) {  // one rollout per lane, device noise (plan_launch's predicate)
+    if (BT == 256 && LPR == 1 && inl) return mppi_plan_kernel<256, 1, true, true>;
+    if (BT == 512 && LPR == 1 && inl) return mppi_plan_kernel<512, 1, true, true>;
+    return nullptr;
+  }
 #define MP_PLAN_CASE(bt, lpr) \
   if (BT == bt && LPR == lpr) return inl ? mppi_plan_kernel<bt, lpr, true> : mppi_plan_kernel<bt, lpr, false>;
   MP_PLAN_CASE(128, 1)
@@ -1002,7 +1043,22 @@ static int plan_launch(mp_ctx* ctx, const MppiDev& D, int S, const double* X0, c
   A.lds_ctrl = A.lds_part = -1;
   const bool many = (size_t)S * nb > 256;  // more blocks than CUs: keep two per CU resident
   const size_t budget = many ? kCoLds : kMaxLds;
-  if ((size_t)(off + (ctrl_words > part_words ? ctrl_words : part_words)) * 8 <= budget) {
+  // The lean instance (mppi_plan_kernel<.., LEAN>) for the common collecting call: one rollout per lane,
+  // device noise, no circle obstacles, the grid in LDS, the control cost on, both collection outputs, and
+  // K < 2^27 (32-bit lane offsets of 16 K bytes).  Such a call keeps no control lists in LDS: they go to
+  // coll_ctrl anyway, and the block partial sums them from there over the same rollouts in the same order
+  // (the LDS path only adds the inactive lanes' 0.0 * u).
+  // (test hook) MPGPU_PLAN_LEAN=0 forces the generic instance and its LDS choice, read per call as MPGPU_LPR is.
+  const char* lean_s = getenv("MPGPU_PLAN_LEAN");
+  const bool lean = !(lean_s && lean_s[0] == '0' && !lean_s[1]) && LPR == 1 && (BT == 256 || BT == 512) && A.inline_noise &&
+                    D.n_obs == 0 && A.grid && A.lds_grid >= 0 && D.ctrl_cost && coll_traj && coll_ctrl &&
+                    K < (1 << 27);
+  if (lean) {
+    if ((size_t)(off + part_words) * 8 <= budget) {
+      A.lds_part = off;
+      off += part_words;
+    }
+  } else if ((size_t)(off + (ctrl_words > part_words ? ctrl_words : part_words)) * 8 <= budget) {
     A.lds_ctrl = A.lds_part = off;
     off += ctrl_words > part_words ? ctrl_words : part_words;
   } else if ((size_t)(off + part_words) * 8 <= budget) {
@@ -1024,6 +1080,9 @@ static int plan_launch(mp_ctx* ctx, const MppiDev& D, int S, const double* X0, c
         for (bool inl : {false, true})
           MP_HIP(ctx, hipFuncSetAttribute((const void*)plan_kernel_for(bt, lpr, inl),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds));
+    for (int bt : {256, 512})
+      MP_HIP(ctx, hipFuncSetAttribute((const void*)plan_kernel_for(bt, 1, true, true),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds));
     ctx->mppi_lds_attr = true;
   }
   // deferred final rollout: snapshot ring slot of this call, free once the final rollout of
@@ -1064,7 +1123,7 @@ static int plan_launch(mp_ctx* ctx, const MppiDev& D, int S, const double* X0, c
   {
     MppiDev Dl = D;
     void* args[] = {(void*)&Dl, (void*)&A};
-    MP_HIP(ctx, hipExtLaunchKernel((const void*)plan_kernel_for(BT, LPR, A.inline_noise != 0), grd, dim3(BT), args,
+    MP_HIP(ctx, hipExtLaunchKernel((const void*)plan_kernel_for(BT, LPR, A.inline_noise != 0, lean), grd, dim3(BT), args,
                                    shmem, ctx->stream, t_start, t_stop, 0));
   }
   MP_HIP(ctx, hipGetLastError());

@@ -185,17 +185,18 @@ __device__ __forceinline__ GridK grid_k(const MppiDev& P, int side) {
   g.ok = P.gnx > 0 && !mpj_div_out(P.gdx) && !mpj_div_out(P.gdy);
   return g;
 }
-template <int LPR = 2>
+// LEAN (the plan kernel's lean instance): no circle obstacles and a grid, known at compile time.
+template <int LPR = 2, bool LEAN = false>
 __device__ __forceinline__ double obstacle_cost(const MppiDev& P, const double* x, const double* obs,
                                                 const unsigned char* grid, int* ok, int side, const GridK& gk) {
   double c = 0.0;
-  for (int o = 0; o < P.n_obs; o++) {
+  for (int o = 0; !LEAN && o < P.n_obs; o++) {
     const double dx = x[0] - obs[3 * o], dy = x[1] - obs[3 * o + 1], R = obs[3 * o + 2];
     const int hit = dx * dx + dy * dy <= R * R;
     *ok &= !hit;
     c = (hit ? c + P.obs_pen : c);
   }
-  if (P.gnx > 0) {
+  if (LEAN || P.gnx > 0) {
     double fx, fy;
     if (LPR == 2) {  // cell coordinates: even lane divides x, odd lane y, one DPP swap
       const double f = mpj_div_gn(side ? x[1] - P.gy0 : x[0] - P.gx0, side ? P.gdy : P.gdx, gk.rx, gk.ok);
@@ -233,7 +234,9 @@ __device__ __forceinline__ void rollout_tab_fill(double* tab, const MppiDev& P, 
 }
 
 // BoundEvaluation, MPPIUtils.jl:135-151 (branch-free, same accumulation order); bnd = tab + kTabBnd
-__device__ __forceinline__ double bound_cost(const MppiDev& P, const double* bnd, const double* x, int* ok) {
+// BndP: `const double*`, or the same address as an LDS pointer (bound_cost_lds).
+template <class BndP>
+__device__ __forceinline__ double bound_cost(const MppiDev& P, BndP bnd, const double* x, int* ok) {
   // an opaque copy of the address: the 14 loads stay inside the step (hoisted out of the rollout loop they
   // would hold 28 VGPRs across it)
   asm volatile("" : "+v"(bnd));
@@ -254,6 +257,14 @@ __device__ __forceinline__ double bound_cost(const MppiDev& P, const double* bnd
     }
   }
   return c;
+}
+
+// The same with the block addressed as LDS (the plan kernel's lean instance): behind the opaque copy a
+// plain pointer is a flat one -- flat loads, which fetch the LDS aperture back every step and whose
+// vmcnt wait also covers the step's TrajectoryCollection stores -- while an LDS pointer keeps ds_read.
+typedef __attribute__((address_space(3))) const double* mp_lds_cdp;
+__device__ __forceinline__ double bound_cost_lds(const MppiDev& P, const double* bnd, const double* x, int* ok) {
+  return bound_cost(P, (mp_lds_cdp)bnd, x, ok);
 }
 
 // ------------------------------------------------------------------ noise
@@ -334,6 +345,27 @@ struct TrajOut {
   double* p;
   long long rs, cs;
 };
+__device__ __forceinline__ bool traj_on(const TrajOut& T) { return T.p != nullptr; }
+// The TrajectoryCollection seen from one wave (the plan kernel's lean instance): state i of the current
+// step at base + i*cs + off bytes.  base is wave-uniform (kernel arguments, blockIdx and the step only) and
+// moves by cs per row on the scalar unit; off = 8*k, the lane's rollout, is fixed for the rollout.  The
+// stores then take the scalar-base, 32-bit vector-offset form: no per-lane 64-bit address arithmetic.
+struct TrajUni {
+  unsigned long long base;  // address of the current row (global memory)
+  unsigned off;
+  unsigned cs;  // 8*K bytes (K < 2^27); a step's rows are 7*cs apart
+};
+__device__ __forceinline__ bool traj_on(const TrajUni&) { return true; }
+// Global-memory address from a wave-uniform base and a 32-bit lane offset in bytes.  Both are opaque
+// register copies (scalar, vector) right at the store, so the address stays this sum as written and the
+// store takes the scalar-base form; left visible, the optimiser forms one per-lane 64-bit pointer before
+// the loop and advances it on the vector unit.  Both keep the copy (no register move to preserve the old value).
+typedef __attribute__((address_space(1))) char mp_gchar;
+__device__ __forceinline__ mp_gchar* uni_addr(unsigned long long& base, unsigned& off) {
+  asm volatile("" : "+s"(base));
+  asm volatile("" : "+v"(off));
+  return reinterpret_cast<mp_gchar*>(base) + (size_t)off;
+}
 
 // The even lane of the pair stores x[0..3], the odd lane x[4..6] (LPR 1: the lane all 7).
 // TrajectoryCollection states are written once and read only by the caller: non-temporal stores
@@ -344,6 +376,17 @@ struct TrajOut {
 __device__ __forceinline__ void st_state(double* a, double v) {
   if (MPPI_NT_STATE) __builtin_nontemporal_store(v, a);
   else *a = v;
+}
+template <int LPR = 2>
+__device__ __forceinline__ void store_state(TrajUni& T, int, const double* x, int) {
+  static_assert(LPR == 1, "uniform-base stores: one rollout per lane");
+#pragma unroll
+  for (int i = 0; i < 7; i++) {
+    auto* q = reinterpret_cast<__attribute__((address_space(1))) double*>(uni_addr(T.base, T.off));
+    if (MPPI_NT_STATE) __builtin_nontemporal_store(x[i], q);
+    else *q = x[i];
+    T.base += T.cs;  // after the seven rows: the next step's
+  }
 }
 template <int LPR = 2>
 __device__ __forceinline__ void store_state(const TrajOut& T, int j, const double* x, int side) {
@@ -376,19 +419,21 @@ __device__ __forceinline__ void ctrl_cost_row(const MppiDev& P, double un0, doub
 // control of step j.  traj.p (optional) gets the H+1 states (store_state).
 // cq: the control-cost rows [H][2] (ctrl_cost_row), or nullptr to evaluate them per step.
 // Returns cost_total; *feas = constraint.
-template <int LPR = 2, class CtrlFn, class StoreFn>
+// LEAN: the optional features fixed at compile time (no circle obstacles, a grid, the control cost from cq).
+template <int LPR = 2, bool LEAN = false, class CtrlFn, class StoreFn, class TrajT>
 __device__ __forceinline__ double rollout_pair(const MppiDev& P, const double* X0, const double* goal,
                                                const double* obs, const unsigned char* grid,
                                                const double* unom, int side, CtrlFn ctrl, StoreFn store,
-                                               const TrajOut& traj, int* feas, const double* atab,
+                                               const TrajT& traj_, int* feas, const double* atab,
                                                const double* cq = nullptr) {
+  TrajT traj = traj_;
   double x[7];
 #pragma unroll
   for (int i = 0; i < 7; i++) x[i] = X0[i];
   const PairK pk = pair_k(side);
   const LaneK lk = lane_k();
   const GridK gk = grid_k<LPR>(P, side);
-  if (traj.p) store_state<LPR>(traj, 0, x, side);
+  if (traj_on(traj)) store_state<LPR>(traj, 0, x, side);
   double sum = 0.0;
   int ok_all = 1;
   for (int j = 0; j < P.H; j++) {
@@ -398,8 +443,8 @@ __device__ __forceinline__ double rollout_pair(const MppiDev& P, const double* X
     int okc = 1, okb = 1;
     double cc = 0.0, cb = 0.0;
     if (j > 0) {
-      cc = obstacle_cost<LPR>(P, x, obs, grid, &okc, side, gk);
-      cb = bound_cost(P, atab + kTabBnd, x, &okb);
+      cc = obstacle_cost<LPR, LEAN>(P, x, obs, grid, &okc, side, gk);
+      cb = LEAN ? bound_cost_lds(P, atab + kTabBnd, x, &okb) : bound_cost(P, atab + kTabBnd, x, &okb);
     }
     const double pc = run_cost(x, u[0], u[1]);
     double k1[7], k2[7], x2[7];
@@ -424,10 +469,10 @@ __device__ __forceinline__ double rollout_pair(const MppiDev& P, const double* X
 #pragma unroll
     for (int i = 0; i < 7; i++) x[i] = x[i] + P.dt * (k1[i] + k2[i]) / 2;
     double cj = pc + cb + cc;
-    if (P.ctrl_cost) {
+    if (LEAN || P.ctrl_cost) {
       const double un0 = unom[2 * j], un1 = unom[2 * j + 1];
       double t[2];
-      if (cq) {
+      if (LEAN || cq) {
         t[0] = cq[2 * j];
         t[1] = cq[2 * j + 1];
       } else {
@@ -438,13 +483,13 @@ __device__ __forceinline__ double rollout_pair(const MppiDev& P, const double* X
     }
     sum = sum + cj;
     ok_all &= okc & okb;
-    if (traj.p) store_state<LPR>(traj, j + 1, x, side);
+    if (traj_on(traj)) store_state<LPR>(traj, j + 1, x, side);
   }
   {  // terminal (:49-54): only the running cost of the extra RK2 step is used
     int okc = 1, okb = 1;
     const double pc = run_cost(x, 0.0, 0.0);
-    const double cc = obstacle_cost<LPR>(P, x, obs, grid, &okc, side, gk);
-    const double cb = bound_cost(P, atab + kTabBnd, x, &okb);
+    const double cc = obstacle_cost<LPR, LEAN>(P, x, obs, grid, &okc, side, gk);
+    const double cb = LEAN ? bound_cost_lds(P, atab + kTabBnd, x, &okb) : bound_cost(P, atab + kTabBnd, x, &okb);
     sum = sum + (pc + cb + cc);
     ok_all &= okc & okb;
   }
