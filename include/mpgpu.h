@@ -171,7 +171,10 @@ int mp_mppi_plan_dev(mp_ctx* ctx, const mp_mppi_params* p, int32_t S, const doub
  * full control list, 0 for DWA's constant controls [S][K][2]); no clamping.
  * U_nom[S][H][2] is used only when p->ctrl_cost != 0.
  * out: traj[S][K][H+1][7] (optional), cost[S][K], feas[S][K],
- *      argmin[S] (optional; first minimum, Julia `minimum`/`argmin` on cost).
+ *      argmin[S] (optional; 0-based index of the first minimum of cost[s][:] under Julia's
+ *      `isless`, what `minimum` over the holders picks (DWAUtils.jl:152, types.jl:9): a NaN cost
+ *      is the greatest value, -0.0 < +0.0, the lowest index among equals.  Not Julia's
+ *      `argmin(cost)`, which returns the index of a NaN).
  * p->K is ignored; K is the argument.
  */
 int mp_rollout(mp_ctx* ctx, const mp_mppi_params* p, int32_t S, int32_t K, const double* X0,

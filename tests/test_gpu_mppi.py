@@ -7,6 +7,10 @@ Tolerances (floating point, fp64 like the reference):
     per-block online-softmax partials (exp(a)·exp(b) vs exp(a+b), tree sums) where the
     reference sums sequentially (SURVEY §8c: "<= 1e-9 for weighted controls");
   * final trajectory / cost (rolled out from MPPICtrl): rtol 1e-9.
+
+mp_rollout and mp_vehicle_euler appear here only through the two CSV replays (DWAPlan's one call shape, the
+100-step plant); their direct parity with the oracle -- per-step and batched controls, ragged K, every output,
+the argmin's ties and NaN order, the plant's partial blocks -- lives in tests/test_gpu_rollout.py.
 """
 import os
 
