@@ -491,7 +491,7 @@ int mp_bfs_plan(mp_ctx* ctx, int32_t B, int32_t nx, int32_t ny, const double* bo
                 int32_t* n_nodes, int32_t* pop_seq, int32_t* path, int32_t* path_n, double* path_length);
 
 /* ----------------------------------------------------------- RRT / RRT* */
-#define MP_RRT_MAX_ITER 1000000 /* cap on n_iter (the tree workspace is 48 bytes per node and scene) */
+#define MP_RRT_MAX_ITER 1000000 /* cap on n_iter (the tree workspace is 48 bytes per node and scene; 64 for mp_rrtnh_plan) */
 
 /* Settings mirror RRTSettings (PathPlanning/RRT/src/types.jl:19-39). */
 typedef struct mp_rrt_params {
@@ -543,6 +543,58 @@ int mp_rrt_plan(mp_ctx* ctx, const mp_rrt_params_t* p, int32_t B, const double* 
                 const double* uniforms, int32_t* n_nodes, int32_t* status, int32_t* best_idx, double* best_cost,
                 double* loc, double* cost, int32_t* parent, int32_t* path_idx, int32_t* path_n,
                 int32_t* counters);
+
+/*
+ * mp_rrtnh_plan — planRRT! of the car-like planner (PathPlanning/RRTNonholonomic/src/rrt_utils.jl:528-583) for B
+ * independent scenes in one launch, one workgroup per scene, the whole sampling loop on the device.  Nodes are
+ * poses [x, y, psi].  Per iteration: sampleRRT (:18-44); the nearest pose of the BallTree snapshot under
+ * MyMetrics (types.jl:9-23; the snapshot is rebuilt every buffer_size registered nodes, :558-561); steer
+ * (:292-365, both branches, the |dx| <= 0.01 -> 0.01 clamp, adjustdist = grow_max) with ProjectionStates
+ * (:208-238), get_max_ang_ratio, get_max_yawangle, DistToDeltaXY, decide_proj and FromProj2Real; collision
+ * (:458-498) in the reference's order: the bound test on the second pose, InitialCheck && FeasibilityClassifier
+ * on the rounded projection of the directed edge (the classifier's one-sided theta test as written there), then
+ * both end points against every circle with <=; registerNode; with rrt_star the near set (:546-549), rewire
+ * (:392-414: root_idx = min_idx, the cost of ProjectionStates(near, new), the test collision(new, near);
+ * chooseParents stays unused, as there) and costPropogation (:416-431).  Then findBestIdx (:585-593) over all
+ * nodes by (x, y) and getBestIdxs.  The settings are mp_rrt_params (RRTSettings has the same live fields; the
+ * reference's grow_dist is [1, 3]).
+ * Constants, as in the reference: the near-set cap 30 (:547), the radius cap 24 (:372, nearDisk = min(gamma *
+ * (log n / n), 24), gamma = 6*W*H*5, n = sample_idx after registering), max_ang = 0.1 (:116), InitialCheck's box
+ * dx in [1, 3], dy in [-1, 1], dpsi in [-0.35, 0.35] (:240-258), and get_max_yawangle's two cubics (:120-145).
+ * in : bound[B][4] (xmin, xmax, ymin, ymax), start[B][3] (x, y, psi), goal[B][2] (ending_ang is never read by
+ *      planRRT!), obstacles / obs_count / n_obs as mp_rrt_plan,
+ *      uniforms[B][n_iter][6]: (u_bias, u_x, u_y, u_psi, u_ratio, u_yaw) in [0, 1) per iteration, in the
+ *      reference's draw order.  The library draws no random numbers: u_bias < bias_rate makes the sample the
+ *      goal, otherwise it is (u_x*(xmax-xmin)+xmin, u_y*(ymax-ymin)+ymin); psi = (u_psi-0.5)*2*pi either way;
+ *      u_ratio is used only where steer draws ang_ratio (:309, :350), u_yaw always (:287).  Slots the
+ *      reference would not draw are ignored.
+ * out: n_nodes[B], status[B] (1 :Solved, 0 :NotSolved), best_idx[B] (0 when not solved), best_cost[B] (0.0
+ *      when not solved).
+ * optional (NULL: not returned), node i (1-based) in row i - 1, rows past n_nodes zero:
+ *      state[B][n_iter+1][3], cost[B][n_iter+1], parent[B][n_iter+1] (node 1: -1),
+ *      path_idx[B][n_iter+1] with path_n[B] (both or neither): getBestIdxs, goal side first, ending in 1,
+ *      counters[B][8]: 0 samples rejected by the bound test, 1 by kinematics, 2 by a circle, 3 rewired edges,
+ *      4 near sets that reached the cap, 5 steers on the in-range branch, 6 steers that drew ang_ratio, 7 near
+ *      sets whose radius was below 24.
+ * Defined differently from the reference:
+ *   - tree queries are brute force over the snapshot under MyMetrics: the nearest node is the minimum metric
+ *     value, the lowest index on ties; the near set is every snapshot node with metric <= r, and from 30 such
+ *     nodes on the 30 smallest by (metric, index).  MyMetrics is not a metric, so the pruning of
+ *     NearestNeighbors' BallTree has no defined answer to pin against: a deviation, not an approximation.  The
+ *     goal set is dx*dx + dy*dy <= goal_tolerance^2, minimum cost, lowest index on ties;
+ *   - the 100 s wall-clock break (:563-566) is dropped: all n_iter samples are drawn;
+ *   - the node capacity is n_iter + 1.
+ * round(v, digits = d) is rint(v*10^d)/10^d, x^2 and x^3 are x*x and x*x*x, n-ary + and * fold left, norm of a
+ * 2-vector is sqrt(v1*v1 + v2*v2) and dot of two 2-vectors is fma(x1, y1, x0*y0).  neural_cost of a zero
+ * distance is Inf or NaN by IEEE, and then no comparison passes.
+ * Errors are mp_rrt_plan's: n_iter outside 1 .. MP_RRT_MAX_ITER, buffer_size < 1 and non-finite bounds, start
+ * or goal return MP_ERR_INVALID before anything is launched or written; a propagation queue longer than the
+ * node count returns MP_ERR_NUMERIC. */
+int mp_rrtnh_plan(mp_ctx* ctx, const mp_rrt_params_t* p, int32_t B, const double* bound, const double* start,
+                  const double* goal, int32_t n_obs, const int32_t* obs_count, const double* obstacles,
+                  const double* uniforms, int32_t* n_nodes, int32_t* status, int32_t* best_idx, double* best_cost,
+                  double* state, double* cost, int32_t* parent, int32_t* path_idx, int32_t* path_n,
+                  int32_t* counters);
 
 /* ------------------------------------------------------- path tracker */
 /* Settings of the Hybrid A* path tracker (PathPlanning/HybridAstar/main_Tracker.jl:42-72). */

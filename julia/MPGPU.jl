@@ -29,7 +29,7 @@ module MPGPU
 using Interpolations: interpolate, Gridded, Constant, Previous, linear_interpolation   # as the reference drivers
 
 export MPPIPlan, MPPIClosedLoop, planHybridAstar!, mppi_plan_batch, mppi_plan_sharded, comm_init, mppi_closed_loop_batch,
-       rollout_batch, ha_expand, ha_rs_connect, ha_astar_table, astar_plan_batch, dka_plan_batch, bfs_plan_batch, rrt_plan_batch,
+       rollout_batch, ha_expand, ha_rs_connect, ha_astar_table, astar_plan_batch, dka_plan_batch, bfs_plan_batch, rrt_plan_batch, rrtnh_plan_batch,
        ha_allpath, ha_neighbor_origin, retrieve_batch!, track_batch!, ilqr_rollout, ilqr_backward!, ilqr_forward!,
        ilqr_solve!, vehicle_euler!, ctx_join
 
@@ -590,6 +590,39 @@ function rrt_plan_batch(p::RrtParams, bound::Matrix{Float64}, start::Matrix{Floa
         best, bcost, loc, cost, parent, path, pn, counters), c)
     return (; n_nodes = nn, status, best_idx = best, best_cost = bcost, loc, cost, parent, path_idx = path, path_n = pn,
             counters)
+end
+
+"""
+    rrtnh_plan_batch(p, bound, start, goal, obstacles, uniforms; obs_count = nothing)
+
+planRRT! of the car-like planner (PathPlanning/RRTNonholonomic/src/rrt_utils.jl:528-583) for B scenes in one launch
+(mp_rrtnh_plan): bound (4, B) = BoundPosition, start (3, B) = [x, y, psi], goal (2, B), obstacles (3, n_obs, B)
+circles with `obs_count[b]` of them counting (nothing: all), uniforms (6, n_iter, B) = (u_bias, u_x, u_y, u_psi,
+u_ratio, u_yaw) per iteration, e.g. `rand(6, p.n_iter, B)`.  `p` is the RrtParams of `rrt_plan_batch`; the
+reference's grow_dist is [1, 3].  Returns n_nodes, status (1 = :Solved), best_idx, best_cost, the tree (state
+(3, n_iter+1, B), cost, parent; 1-based node indices, parent of node 1 is -1), the best path's indices (goal side
+first, `path_n[b]` of them) and the eight counters (samples rejected by the bound test, by kinematics, by a circle;
+rewired edges; capped near sets; in-range steers; steers that drew ang_ratio; near sets with a radius below 24).
+"""
+function rrtnh_plan_batch(p::RrtParams, bound::Matrix{Float64}, start::Matrix{Float64}, goal::Matrix{Float64},
+                          obstacles::Array{Float64,3}, uniforms::Array{Float64,3}; obs_count = nothing)
+    B = size(bound, 2); cap = Int(p.n_iter) + 1
+    n_obs = size(obstacles, 2)
+    size(start) == (3, B) || error("rrtnh_plan_batch: start must be (3, B)")
+    size(uniforms) == (6, Int(p.n_iter), B) || error("rrtnh_plan_batch: uniforms must be (6, n_iter, B)")
+    oc = obs_count === nothing ? Int32[] : Vector{Int32}(obs_count)
+    nn = zeros(Int32, B); status = zeros(Int32, B); best = zeros(Int32, B); bcost = zeros(B)
+    state = zeros(3, cap, B); cost = zeros(cap, B); parent = zeros(Int32, cap, B)
+    path = zeros(Int32, cap, B); pn = zeros(Int32, B); counters = zeros(Int32, 8, B)
+    c = ctx()
+    check(GC.@preserve bound start goal obstacles uniforms oc nn status best bcost state cost parent path pn counters ccall((:mp_rrtnh_plan, libmpgpu), Cint,
+        (Ptr{Cvoid}, Ref{RrtParams}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Int32}, Ptr{Float64},
+         Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32},
+         Ptr{Int32}, Ptr{Int32}, Ptr{Int32}),
+        c, p, B, bound, start, goal, n_obs, obs_count === nothing ? C_NULL : pointer(oc), obstacles, uniforms, nn, status,
+        best, bcost, state, cost, parent, path, pn, counters), c)
+    return (; n_nodes = nn, status, best_idx = best, best_cost = bcost, state, cost, parent, path_idx = path,
+            path_n = pn, counters)
 end
 
 """

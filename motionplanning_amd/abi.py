@@ -202,6 +202,7 @@ SIGNATURES = {
     "mp_dka_plan": (ctypes.c_int, [_V, _I, _I, _I, _V, _V, _V, _I] + [_V] * 9),
     "mp_bfs_plan": (ctypes.c_int, [_V, _I, _I, _I, _V, _V, _V, _I] + [_V] * 8),
     "mp_rrt_plan": (ctypes.c_int, [_V, ctypes.POINTER(RRTParams), _I, _V, _V, _V, _I] + [_V] * 13),
+    "mp_rrtnh_plan": (ctypes.c_int, [_V, ctypes.POINTER(RRTParams), _I, _V, _V, _V, _I] + [_V] * 13),
     "mp_ha_retrieve_path": (ctypes.c_int, [_V, _I, _V, _V, _V, _I] + [_V] * 8),
     "mp_ha_track": (ctypes.c_int, [_V, ctypes.POINTER(TrackParams), _I, _V, _V, _V, _I] + [_V] * 6 + [_I]),
     "mp_math_eval": (ctypes.c_int, [_V, _I, ctypes.c_int64, _V, _V, _V]),

@@ -124,10 +124,10 @@ enum {
   WS_AS_MASK,     // ... free-cell masks
   WS_AS_TABLE,    // ... mp_astar_plan's outputs / the Hybrid A* heuristic table
   WS_AS_ERR,      // ... pop-cap flag
-  WS_RRT_IN,      // RRT (rrt.hip): bounds, starts, goals, obstacles
+  WS_RRT_IN,      // RRT (rrt.hip, and rrtnh.hip, which shares these slots): bounds, starts, goals, obstacles
   WS_RRT_CNT,     // ... obstacle counts
   WS_RRT_UNI,     // ... uniforms
-  WS_RRT_TREE,    // ... tree state (48 bytes per node and scene)
+  WS_RRT_TREE,    // ... tree state (48 bytes per node and scene; rrtnh.hip 64)
   WS_RRT_OUT,     // ... per-scene results and paths
   WS_COUNT
 };
