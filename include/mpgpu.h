@@ -490,6 +490,35 @@ int mp_bfs_plan(mp_ctx* ctx, int32_t B, int32_t nx, int32_t ny, const double* bo
                 const double* goal_real, int32_t n_obs, const double* circles, int32_t* found, int32_t* pops,
                 int32_t* n_nodes, int32_t* pop_seq, int32_t* path, int32_t* path_n, double* path_length);
 
+/* ------------------------------------- grid planners: large grids, masks */
+#define MP_GRID_ASTAR 0
+#define MP_GRID_DKA 1
+#define MP_GRID_BFS 2
+#define MP_GRID_OBS_MASK 1     /* obs_kind: caller-supplied free-cell mask */
+#define MP_GRID_FORCE_GLOBAL 1 /* flags bit 0: run the global-memory kernels whatever the size */
+#define MP_GRID_MAX_CELLS (1 << 22)
+
+/* mp_astar_plan / mp_dka_plan / mp_bfs_plan (planner = MP_GRID_ASTAR / MP_GRID_DKA / MP_GRID_BFS) without the
+ * 51 x 51 limit, and with occupancy masks.  Arguments, output layouts, optional outputs, the pop bound
+ * 2*(nx*ny+1) (MP_ERR_NUMERIC) and the cases defined where the reference fails are those of the three calls
+ * above; final_cost may be NULL for MP_GRID_BFS and is ignored there.
+ *   nx, ny >= 2 and nx*ny <= MP_GRID_MAX_CELLS (MP_ERR_INVALID beyond).
+ *   obs_kind 3 (circles): every planner.  obs_kind 5 (blocks): MP_GRID_ASTAR only, as in the reference
+ *     (MP_ERR_INVALID with the other two).
+ *   obs_kind MP_GRID_OBS_MASK: obstacles is const uint8_t mask[B][ny][nx], cell (ix, iy) at (iy-1)*nx + ix-1,
+ *     nonzero = free; n_obs is ignored.  An extension: the result is the reference planner's with
+ *     checkObsSafety replaced by the table lookup.
+ * With nx*ny <= 51*51 and MP_GRID_FORCE_GLOBAL clear the searches run the kernels of the three calls above (one
+ * wavefront each, node table in LDS).  Otherwise one workgroup runs each search on node tables in a device
+ * workspace: 32 bytes per cell and search for A* and Dijkstra, 12 for BFS, beside the outputs' 12.  A* and
+ * Dijkstra pop the open entry with the smallest (f, number), numbers handed out so that the order is the
+ * reference's stable sort; every output is the same either way.  A workspace that cannot
+ * be had (mp_ctx_set_workspace_limit, or the device is full) returns MP_ERR_NOMEM before anything is launched. */
+int mp_grid_plan(mp_ctx* ctx, int32_t planner, int32_t flags, int32_t B, int32_t nx, int32_t ny, const double* bound,
+                 const double* start_real, const double* goal_real, int32_t obs_kind, int32_t n_obs,
+                 const void* obstacles, double* final_cost, int32_t* found, int32_t* pops, int32_t* n_nodes,
+                 int32_t* pop_seq, int32_t* path, int32_t* path_n, double* path_length);
+
 /* ----------------------------------------------------------- RRT / RRT* */
 #define MP_RRT_MAX_ITER 1000000 /* cap on n_iter (the tree workspace is 48 bytes per node and scene; 64 for mp_rrtnh_plan) */
 

@@ -29,7 +29,7 @@ module MPGPU
 using Interpolations: interpolate, Gridded, Constant, Previous, linear_interpolation   # as the reference drivers
 
 export MPPIPlan, MPPIClosedLoop, planHybridAstar!, mppi_plan_batch, mppi_plan_sharded, comm_init, mppi_closed_loop_batch,
-       rollout_batch, ha_expand, ha_rs_connect, ha_astar_table, astar_plan_batch, dka_plan_batch, bfs_plan_batch, rrt_plan_batch, rrtnh_plan_batch,
+       rollout_batch, ha_expand, ha_rs_connect, ha_astar_table, astar_plan_batch, dka_plan_batch, bfs_plan_batch, grid_plan_batch, rrt_plan_batch, rrtnh_plan_batch,
        ha_allpath, ha_neighbor_origin, retrieve_batch!, track_batch!, ilqr_rollout, ilqr_backward!, ilqr_forward!,
        ilqr_solve!, vehicle_euler!, ctx_join
 
@@ -548,6 +548,41 @@ function bfs_plan_batch(mapbound, bound::Matrix{Float64}, start_real::Matrix{Flo
         c, B, nx, ny, bound, start_real, goal_real, n_obs, n_obs == 0 ? C_NULL : pointer(circles), found, pops, nn,
         seq, path, pn, plen), c)
     return (; found, loop_count = pops, n_nodes = nn, pop_sequence = seq, bfspath = path, path_n = pn,
+            path_length = plen)
+end
+
+const MP_GRID_ASTAR = Int32(0)
+const MP_GRID_DKA = Int32(1)
+const MP_GRID_BFS = Int32(2)
+const MP_GRID_OBS_MASK = Int32(1)
+const MP_GRID_FORCE_GLOBAL = Int32(1)
+
+"""
+    grid_plan_batch(planner, mapbound, bound, start_real, goal_real, obstacles; flags = 0)
+
+planAstar! / planDKA! / planBFS! (planner = MP_GRID_ASTAR / MP_GRID_DKA / MP_GRID_BFS) for B searches on grids
+of up to 2^22 cells (mp_grid_plan): mapbound = (nx, ny), bound (4, B), start_real / goal_real (2, B).  obstacles
+is either a Float64 array (3 or 5, n_obs, B) of circles or (A* only) blocks, or a UInt8 array (nx, ny, B) of
+free-cell masks, nonzero = free (cell (ix, iy) of search b at mask[ix, iy, b]).  Returns what astar_plan_batch
+returns (final_cost stays 0 for BFS), the path as `path`.
+"""
+function grid_plan_batch(planner, mapbound, bound::Matrix{Float64}, start_real::Matrix{Float64},
+                         goal_real::Matrix{Float64}, obstacles::Union{Array{Float64,3},Array{UInt8,3}}; flags = 0)
+    nx, ny = Int(mapbound[1]), Int(mapbound[2])
+    B = size(bound, 2); M = nx * ny + 1
+    masked = eltype(obstacles) == UInt8
+    masked && size(obstacles) != (nx, ny, B) && error("grid_plan_batch: the masks must be (nx, ny, B)")
+    kind = masked ? MP_GRID_OBS_MASK : Int32(size(obstacles, 1)); n_obs = masked ? 0 : size(obstacles, 2)
+    cost = zeros(B); plen = zeros(B)
+    found = zeros(Int32, B); pops = zeros(Int32, B); nn = zeros(Int32, B); pn = zeros(Int32, B)
+    seq = zeros(Int32, 2M, B); path = zeros(Int32, M, B)
+    c = ctx()
+    check(GC.@preserve bound start_real goal_real obstacles cost plen found pops nn pn seq path ccall((:mp_grid_plan, libmpgpu), Cint,
+        (Ptr{Cvoid}, Int32, Int32, Int32, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Ptr{Cvoid},
+         Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}),
+        c, planner, flags, B, nx, ny, bound, start_real, goal_real, kind, n_obs,
+        !masked && n_obs == 0 ? C_NULL : pointer(obstacles), cost, found, pops, nn, seq, path, pn, plen), c)
+    return (; final_cost = cost, found, loop_count = pops, n_nodes = nn, pop_sequence = seq, path, path_n = pn,
             path_length = plen)
 end
 

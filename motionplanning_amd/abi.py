@@ -201,6 +201,7 @@ SIGNATURES = {
     "mp_astar_plan": (ctypes.c_int, [_V, _I, _I, _I, _V, _V, _V, _I, _I] + [_V] * 9),
     "mp_dka_plan": (ctypes.c_int, [_V, _I, _I, _I, _V, _V, _V, _I] + [_V] * 9),
     "mp_bfs_plan": (ctypes.c_int, [_V, _I, _I, _I, _V, _V, _V, _I] + [_V] * 8),
+    "mp_grid_plan": (ctypes.c_int, [_V, _I, _I, _I, _I, _I, _V, _V, _V, _I, _I] + [_V] * 9),
     "mp_rrt_plan": (ctypes.c_int, [_V, ctypes.POINTER(RRTParams), _I, _V, _V, _V, _I] + [_V] * 13),
     "mp_rrtnh_plan": (ctypes.c_int, [_V, ctypes.POINTER(RRTParams), _I, _V, _V, _V, _I] + [_V] * 13),
     "mp_ha_retrieve_path": (ctypes.c_int, [_V, _I, _V, _V, _V, _I] + [_V] * 8),

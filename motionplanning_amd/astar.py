@@ -1,17 +1,19 @@
 """Grid A* — host-side mirror of PathPlanning/Astar/src/{types,setup,astar_utils}.jl over the libmpgpu
-C-ABI (mp_astar_plan).
+C-ABI (mp_astar_plan, mp_grid_plan).
 
 ``defineAstar`` / ``defineAstarobs_`` / ``planAstar_`` keep the reference's names and argument meaning.
-The search runs in the library: one wavefront per search, node table and open list in LDS; ``plan_batch``
-runs B searches that share the grid size, the obstacle kind and the obstacle count in one call.
+The search runs in the library: up to 51 x 51 cells one wavefront per search, node table and open list in LDS;
+above that, and for a searcher that carries an occupancy mask (``defineAstarmask_``), one workgroup per search on
+node tables in device memory (mp_grid_plan).  ``plan_batch`` runs B searches that share the grid size, the obstacle
+kind and the obstacle count in one call.
 """
 import math
-import time
 from dataclasses import dataclass, field
 
 import numpy as np
 
-from .abi import f64, ptr
+from . import _gridsearch
+from .abi import f64
 from .context import default_context
 
 
@@ -28,6 +30,7 @@ class AstarSettings:
     obstacle_list: list = field(default_factory=list)
     x_factor: float = 0.0
     y_factor: float = 0.0
+    free_mask: np.ndarray = None  # defineAstarmask_ (not in the reference): replaces obstacle_list
 
 
 @dataclass
@@ -71,6 +74,12 @@ def defineAstar(realsize=(-50, 0, 50, 100), mapbound=(51, 51), starting_real=(-3
 def defineAstarobs_(a, obstacle_list):
     """defineAstarobs! (setup.jl:27-30): circles [x, y, r] or blocks [x, y, ψ, l/2, w/2]."""
     a.s.obstacle_list = [list(map(float, o)) for o in obstacle_list]
+    a.s.free_mask = None
+
+
+def defineAstarmask_(a, mask):
+    """An occupancy grid in place of the obstacle list: uint8 [ny, nx], nonzero = free (_gridsearch.define_mask)."""
+    _gridsearch.define_mask(a, mask)
 
 
 def TransferCoordinate(a, pos):
@@ -80,8 +89,9 @@ def TransferCoordinate(a, pos):
 
 
 def plan_batch(searchers, ctx=None):
-    """planAstar! for B searchers sharing mapbound, the obstacle kind and the obstacle count."""
+    """planAstar! for B searchers sharing mapbound and either the obstacle kind and count, or all carrying masks."""
     ctx = ctx or default_context()
+    masks = _gridsearch.batch_masks(searchers)
     a0 = searchers[0]
     nx, ny = int(a0.s.mapbound[0]), int(a0.s.mapbound[1])
     n_obs = len(a0.s.obstacle_list)
@@ -90,33 +100,8 @@ def plan_batch(searchers, ctx=None):
         if (int(a.s.mapbound[0]), int(a.s.mapbound[1])) != (nx, ny) or len(a.s.obstacle_list) != n_obs or any(
                 len(o) != kind for o in a.s.obstacle_list):
             raise ValueError("plan_batch: every search needs the same mapbound, obstacle kind and obstacle count")
-    B, M = len(searchers), nx * ny + 1
-    bound = f64([a.s.actualbound for a in searchers])
-    start = f64([a.s.starting_real for a in searchers])
-    goal = f64([a.s.ending_real for a in searchers])
-    obs = f64([a.s.obstacle_list for a in searchers]).reshape(B, n_obs, kind) if n_obs else None
-    cost, plen = np.zeros(B), np.zeros(B)
-    found, pops, nn, pn = (np.zeros(B, np.int32) for _ in range(4))
-    seq = np.zeros((B, 2 * M), np.int32)
-    path = np.zeros((B, M), np.int32)
-    t0 = time.time()
-    ctx.check(ctx.lib.mp_astar_plan(ctx.handle, B, nx, ny, ptr(bound), ptr(start), ptr(goal), kind, n_obs, ptr(obs),
-                                    ptr(cost), ptr(found), ptr(pops), ptr(nn), ptr(seq), ptr(path), ptr(pn),
-                                    ptr(plen)))
-    dt = time.time() - t0
-    for b, a in enumerate(searchers):
-        r = a.r
-        r.final_cost, r.path_length = float(cost[b]), float(plen[b])
-        r.found, r.loop_count, r.n_nodes = bool(found[b]), int(pops[b]), int(nn[b])
-        r.pop_sequence = seq[b, : pops[b]].copy()
-        enc = path[b, : pn[b]].astype(np.int64)
-        # Encode index -> [x y] rows (astarpath); index 0 is a start cell off the grid
-        cells = np.c_[(enc - 1) % nx + 1, (enc - 1) // nx + 1]
-        cells[enc == 0] = a.s.starting_pos
-        r.astarpath = cells
-        r.actualpath = np.array([TransferCoordinate(a, c) for c in cells]).reshape(-1, 2)
-        r.planning_time = dt
-    return searchers
+    obs = f64([a.s.obstacle_list for a in searchers]).reshape(len(searchers), n_obs, kind) if n_obs else None
+    return _gridsearch.run(ctx, "astar", searchers, nx, ny, kind, n_obs, obs, masks, "astarpath")
 
 
 def planAstar_(a, ctx=None):

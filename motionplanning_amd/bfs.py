@@ -2,8 +2,10 @@
 the libmpgpu C-ABI (mp_bfs_plan).
 
 ``defineBFS`` / ``defineBFSobs_`` / ``planBFS_`` keep the reference's names and argument meaning.  The search runs
-in the library, one wavefront per search, a whole level of the queue at a time in the sequential loop's order;
-``plan_batch`` runs B searches that share the grid size in one call, whatever their obstacle counts.
+in the library, a whole level of the queue at a time in the sequential loop's order: one wavefront per search up to
+51 x 51 cells, one workgroup on tables in device memory above that (mp_grid_plan), and for a searcher that carries
+an occupancy mask (``defineBFSmask_``); ``plan_batch`` runs B searches that share the grid size in one call,
+whatever their obstacle counts.
 """
 from dataclasses import dataclass, field
 
@@ -25,6 +27,7 @@ class BFSSetting:
     obstacle_list: list = field(default_factory=list)
     x_factor: float = 0.0
     y_factor: float = 0.0
+    free_mask: np.ndarray = None  # defineBFSmask_ (not in the reference): replaces obstacle_list
 
 
 @dataclass
@@ -56,6 +59,12 @@ def defineBFS(realsize=(-50, 0, 50, 100), mapbound=(51, 51), starting_real=(-3, 
 def defineBFSobs_(bfs, obstacle_list):
     """defineBFSobs! (setup.jl:28-31): circles [x, y, r]."""
     bfs.s.obstacle_list = [list(map(float, o)) for o in obstacle_list]
+    bfs.s.free_mask = None
+
+
+def defineBFSmask_(bfs, mask):
+    """An occupancy grid in place of the obstacle list: uint8 [ny, nx], nonzero = free (_gridsearch.define_mask)."""
+    _gridsearch.define_mask(bfs, mask)
 
 
 def TransferCoordinate(bfs, pos):
@@ -65,7 +74,7 @@ def TransferCoordinate(bfs, pos):
 
 def plan_batch(searchers, ctx=None):
     """planBFS! for B searchers sharing mapbound; shorter obstacle lists are padded with [0, 0, 0] circles."""
-    return _gridsearch.plan_batch(searchers, "mp_bfs_plan", "bfspath", False, ctx=ctx)
+    return _gridsearch.plan_batch(searchers, "bfs", "bfspath", ctx=ctx)
 
 
 def planBFS_(bfs, ctx=None):

@@ -14,6 +14,8 @@
 // bfs_search_kernel planBFS! + FindNewNode, one wavefront per search, level by level: the FIFO never sorts
 //                   and a cell enters it once, so the queue is the pop sequence and a whole level expands
 //                   at once in the sequential loop's order.
+// mp_grid_plan is the same host side (as_plan) without the 51 x 51 limit and with caller-supplied masks: above
+// the limit, or when forced, as_launch hands the searches to gridbig.hip's global-memory kernels.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -21,6 +23,7 @@
 
 #define MPJ_LANE_SAFE 1
 #include "../../include/mp_jlmath.h"
+#include "gridsearch.hpp"
 #include "runtime.hpp"
 
 namespace {
@@ -36,7 +39,6 @@ constexpr unsigned short AS_NOPAR = 0xFFFF;
 constexpr size_t as_lds_bytes(int M, bool dka = false) { return (size_t)M * ((dka ? 2 : 3) * 8 + 3 * 2 + 1); }
 // ... of one breadth-first search: the claim word (uint32), parent and queue (uint16), the state bits (uint8)
 constexpr size_t bfs_lds_bytes(int M) { return (size_t)M * (4 + 2 * 2 + 1); }
-enum { AS_ASTAR = 0, AS_DKA = 1, AS_BFS = 2 };  // as_launch's planner
 
 // The reference's BLAS-dispatched products round as Julia's OpenBLAS does (oracle/or_blas.h), as in
 // hastar.hip: R*pts is dgemm with K = 2, transpose(pts .- bg_pt)*normal_vec is dgemv 'T' on two rows.
@@ -116,49 +118,10 @@ __global__ __launch_bounds__(256) void as_mask_kernel(int scenes, int nx, int ny
   mask[i] = (unsigned char)ok;
 }
 
-struct AsArgs {
-  int nx, ny;
-  int per_scene;  // searches per scene: 1 (start cells in scell), or nx*ny (search q starts in cell q + 1)
-  int cap;        // pop cap
-  const double* geo;          // [scenes][4]
-  const int* scell;           // [searches][2] starting_pos (per_scene == 1)
-  const int* gcell;           // [scenes][2] ending_pos
-  const unsigned char* mask;  // [scenes][nx*ny]
-  double* cost;               // [searches] final_cost (null: breadth-first search has none)
-  int *found, *pops, *n_nodes;  // [searches] (each may be null)
-  int* pop_seq;               // [searches][cap] Encode index per pop, or null
-  int* path;                  // [searches][nx*ny + 1] astarpath as Encode indices, start -> goal, or null
-  int* path_n;                // [searches]
-  double* path_len;           // [searches] astar.r.path_length, or null
-  int* err;                   // [1] a search reached the pop cap
-};
-
 // FindNewNode's directions as written (astar_utils.jl:192); entries 2 and 7 repeat 1 and 3: a repeat finds
 // the node its first occurrence just wrote with the same tentative g and changes nothing
 __device__ const signed char AS_DX[9] = {-1, -1, -1, 1, 1, 1, 0, 1, 0};
 __device__ const signed char AS_DY[9] = {0, -1, -1, -1, 0, 1, -1, -1, 1};
-
-// sum(norm(actualpath[i+1, :] - actualpath[i, :])) (astar_utils.jl:129, dka_utils.jl:112), a left fold over
-// the path's cnt cells, held goal side first in rev
-template <typename T>
-__device__ __forceinline__ double as_path_length(const T* rev, int cnt, int nx, int sx, int sy, double xf, double yf,
-                                                 const double* ge) {
-  double acc = 0.0;
-  double ax = 0.0, ay = 0.0;
-  for (int i = 0; i < cnt; i++) {
-    const int c = rev[cnt - 1 - i];
-    const int px = c == 0 ? sx : (c - 1) % nx + 1, py = c == 0 ? sy : (c - 1) / nx + 1;
-    const double tx = ((double)px - 1.0) * xf + ge[0], ty = ((double)py - 1.0) * yf + ge[1];
-    if (i > 0) {
-      const double ex = tx - ax, ey = ty - ay;
-      const double n = mpj_sqrt(ex * ex + ey * ey);
-      acc = i == 1 ? n : acc + n;
-    }
-    ax = tx;
-    ay = ty;
-  }
-  return acc;
-}
 
 // DKA: planDKA! (dka_utils.jl:69-126, FindNewNode :175-215) -- the same directions, sort and InOpen rule with
 // no temp_h: f = g + 0.0 = g exactly, so f aliases g and the update test reads f (:193)
@@ -434,15 +397,19 @@ bool as_cell(const double* ge, const double* real, int* cell) {
   return true;
 }
 
-// masks + searches on the context stream (no synchronisation).  obs_dev: [scenes][n_obs][kind] on the device.
-int as_launch(mp_ctx* ctx, int planner, int scenes, int kind, int n_obs, const double* obs_dev, AsArgs A) {
+// masks + searches on the context stream (no synchronisation).  obs_dev: [scenes][n_obs][kind] on the device;
+// kind MP_GRID_OBS_MASK: the masks are in WS_AS_MASK already.  node_ws: the node workspace of gridbig.hip's
+// kernels, which then run the searches (null: the LDS kernels, nx*ny <= AS_MAX_CELLS).
+int as_launch(mp_ctx* ctx, int planner, int scenes, int kind, int n_obs, const double* obs_dev, AsArgs A,
+              void* node_ws = nullptr) {
   const int N = A.nx * A.ny;
   unsigned char* mask = (unsigned char*)mp_ws(ctx, WS_AS_MASK, (size_t)scenes * N);
   int* err = (int*)mp_ws(ctx, WS_AS_ERR, sizeof(int));
   if (!mask || !err) return MP_ERR_NOMEM;
   MP_HIP(ctx, hipMemsetAsync(err, 0, sizeof(int), ctx->stream));
   const double* wpts = nullptr;
-  if (n_obs == 0) {  // an empty obstacle list (A* indexes obstacle_list[1]; Dijkstra and BFS loop over 1:0): all free
+  if (kind == MP_GRID_OBS_MASK) {  // the caller's masks, uploaded by as_plan: nothing to compute
+  } else if (n_obs == 0) {  // an empty obstacle list (A* indexes obstacle_list[1]; Dijkstra and BFS loop over 1:0): all free
     MP_HIP(ctx, hipMemsetAsync(mask, 1, (size_t)scenes * N, ctx->stream));
   } else {
     if (kind == 5) {
@@ -460,6 +427,7 @@ int as_launch(mp_ctx* ctx, int planner, int scenes, int kind, int n_obs, const d
   A.mask = mask;
   A.err = err;
   A.cap = 2 * (N + 1);
+  if (node_ws) return gb_launch(ctx, planner, scenes * A.per_scene, node_ws, A);
   const dim3 grid((unsigned)(scenes * A.per_scene));
   if (planner == AS_BFS) {  // 23.4 KB at the largest grid: no attribute to raise
     hipLaunchKernelGGL(bfs_search_kernel, grid, dim3(64), bfs_lds_bytes(N + 1), ctx->stream, A);
@@ -493,18 +461,38 @@ int as_check_err(mp_ctx* ctx) {
   return MP_OK;
 }
 
-// the body of mp_astar_plan / mp_dka_plan / mp_bfs_plan behind their argument checks (final_cost: null for BFS)
+// the body of mp_astar_plan / mp_dka_plan / mp_bfs_plan (max_cells = AS_MAX_CELLS) and of mp_grid_plan behind
+// their argument checks (final_cost: null for BFS).  obs_kind MP_GRID_OBS_MASK (mp_grid_plan only): obstacles is
+// the free-cell mask [B][ny][nx].  Grids above AS_MAX_CELLS, and every grid with force_global, run gridbig.hip's
+// kernels.
 int as_plan(mp_ctx* ctx, int planner, int B, int nx, int ny, const double* bound, const double* start_real,
-            const double* goal_real, int obs_kind, int n_obs, const double* obstacles, double* final_cost, int32_t* found,
-            int32_t* pops, int32_t* n_nodes, int32_t* pop_seq, int32_t* path, int32_t* path_n, double* path_length) {
-  MP_CHECK(ctx, nx >= 2 && ny >= 2 && (long long)nx * ny <= AS_MAX_CELLS,
-           "grid %d x %d: each side must be >= 2 and nx*ny <= %d", nx, ny, AS_MAX_CELLS);
-  MP_CHECK(ctx, obs_kind == 3 || obs_kind == 5, "obstacle kind must be 3 (circles) or 5 (blocks)");
-  MP_CHECK(ctx, n_obs >= 0 && (n_obs == 0 || obstacles), "bad obstacle list");
+            const double* goal_real, int obs_kind, int n_obs, const void* obstacles, double* final_cost, int32_t* found,
+            int32_t* pops, int32_t* n_nodes, int32_t* pop_seq, int32_t* path, int32_t* path_n, double* path_length,
+            int max_cells = AS_MAX_CELLS, bool force_global = false) {
+  MP_CHECK(ctx, nx >= 2 && ny >= 2 && (long long)nx * ny <= max_cells,
+           "grid %d x %d: each side must be >= 2 and nx*ny <= %d", nx, ny, max_cells);
+  const bool masked = max_cells > AS_MAX_CELLS && obs_kind == MP_GRID_OBS_MASK;  // (the three older calls take lists)
+  if (masked) {
+    MP_CHECK(ctx, obstacles != nullptr, "the free-cell mask is NULL");
+    n_obs = 0;
+  } else {
+    MP_CHECK(ctx, obs_kind == 3 || obs_kind == 5, "obstacle kind must be 3 (circles) or 5 (blocks)");
+    MP_CHECK(ctx, n_obs >= 0 && (n_obs == 0 || obstacles), "bad obstacle list");
+  }
   MP_CHECK(ctx, (path != nullptr) == (path_n != nullptr), "the path and path_n go together");
   MP_HIP(ctx, hipSetDevice(ctx->device));
   const int N = nx * ny, M = N + 1, cap = 2 * M;
   const size_t nB = (size_t)B;
+  // every workspace before the first copy or launch: the node tables of the global-memory kernels ...
+  void* node_ws = nullptr;
+  if (N > AS_MAX_CELLS || force_global) {
+    node_ws = mp_ws(ctx, WS_GB_NODE, gb_node_bytes(planner, nB, N));
+    if (!node_ws) return MP_ERR_NOMEM;
+  }
+  // ... the masks, and the outputs: [cost B doubles | path_len B doubles | found, pops, n_nodes, path_n B ints
+  // each | pop_seq | path]
+  char* out = (char*)mp_ws(ctx, WS_AS_TABLE, nB * (16 + 16 + 4 * ((size_t)cap + M)));
+  if (!out || !mp_ws(ctx, WS_AS_MASK, nB * N)) return MP_ERR_NOMEM;
   std::vector<double> ge(4 * nB);
   std::vector<int> sc(2 * nB), gc(2 * nB);
   for (int s = 0; s < B; s++) {
@@ -521,10 +509,9 @@ int as_plan(mp_ctx* ctx, int planner, int B, int nx, int ny, const double* bound
   A.geo = mp_upload(ctx, WS_AS_GEO, ge.data(), ge.size(), &st);
   A.gcell = mp_upload(ctx, WS_AS_GCELL, gc.data(), gc.size(), &st);
   A.scell = mp_upload(ctx, WS_AS_SCELL, sc.data(), sc.size(), &st);
-  const double* dobs = n_obs ? mp_upload(ctx, WS_AS_OBS, obstacles, nB * n_obs * obs_kind, &st) : nullptr;
-  // outputs: [cost B doubles | path_len B doubles | found, pops, n_nodes, path_n B ints each | pop_seq | path]
-  char* out = (char*)mp_ws(ctx, WS_AS_TABLE, nB * (16 + 16 + 4 * ((size_t)cap + M)));
-  if (st || !A.geo || !A.gcell || !A.scell || (n_obs && !dobs) || !out) return st ? st : MP_ERR_NOMEM;
+  const double* dobs = n_obs ? mp_upload(ctx, WS_AS_OBS, (const double*)obstacles, nB * n_obs * obs_kind, &st) : nullptr;
+  if (masked && !mp_upload(ctx, WS_AS_MASK, (const unsigned char*)obstacles, nB * N, &st)) return st ? st : MP_ERR_NOMEM;
+  if (st || !A.geo || !A.gcell || !A.scell || (n_obs && !dobs)) return st ? st : MP_ERR_NOMEM;
   double* dcost = (double*)out;
   A.cost = planner == AS_BFS ? nullptr : dcost;
   A.path_len = dcost + nB;
@@ -538,7 +525,7 @@ int as_plan(mp_ctx* ctx, int planner, int B, int nx, int ny, const double* bound
   A.path = path ? dpath : nullptr;
   if (pop_seq) MP_HIP(ctx, hipMemsetAsync(dseq, 0xff, sizeof(int) * nB * cap, ctx->stream));  // -1 past the pops
   if (path) MP_HIP(ctx, hipMemsetAsync(dpath, 0xff, sizeof(int) * nB * M, ctx->stream));
-  if ((st = as_launch(ctx, planner, B, obs_kind, n_obs, dobs, A))) return st;
+  if ((st = as_launch(ctx, planner, B, obs_kind, n_obs, dobs, A, node_ws))) return st;
   if ((st = mp_download(ctx, final_cost, (const double*)A.cost, nB))) return st;
   if ((st = mp_download(ctx, path_length, (const double*)A.path_len, nB))) return st;
   if ((st = mp_download(ctx, found, (const int32_t*)A.found, nB))) return st;
@@ -610,6 +597,26 @@ int mp_bfs_plan(mp_ctx* ctx, int32_t B, int32_t nx, int32_t ny, const double* bo
   MP_CHECK(ctx, B >= 1 && bound && start_real && goal_real && found && pops && n_nodes, "bad arguments");
   return as_plan(ctx, AS_BFS, B, nx, ny, bound, start_real, goal_real, 3, n_obs, circles, nullptr, found, pops, n_nodes,
                  pop_seq, path, path_n, path_length);
+}
+
+int mp_grid_plan(mp_ctx* ctx, int32_t planner, int32_t flags, int32_t B, int32_t nx, int32_t ny, const double* bound,
+                 const double* start_real, const double* goal_real, int32_t obs_kind, int32_t n_obs,
+                 const void* obstacles, double* final_cost, int32_t* found, int32_t* pops, int32_t* n_nodes,
+                 int32_t* pop_seq, int32_t* path, int32_t* path_n, double* path_length) {
+  if (!ctx) return MP_ERR_INVALID;
+  MP_CHECK(ctx, planner == MP_GRID_ASTAR || planner == MP_GRID_DKA || planner == MP_GRID_BFS,
+           "planner must be MP_GRID_ASTAR, MP_GRID_DKA or MP_GRID_BFS");
+  MP_CHECK(ctx, (flags & ~MP_GRID_FORCE_GLOBAL) == 0, "unknown flags");
+  MP_CHECK(ctx, B >= 1 && bound && start_real && goal_real && (final_cost || planner == MP_GRID_BFS) && found && pops &&
+                    n_nodes,
+           "bad arguments");
+  MP_CHECK(ctx, obs_kind == 3 || obs_kind == 5 || obs_kind == MP_GRID_OBS_MASK,
+           "obstacle kind must be 3 (circles), 5 (blocks) or MP_GRID_OBS_MASK");
+  MP_CHECK(ctx, obs_kind != 5 || planner == MP_GRID_ASTAR, "blocks are obstacles of A* only: Dijkstra and BFS take circles");
+  static_assert(MP_GRID_ASTAR == AS_ASTAR && MP_GRID_DKA == AS_DKA && MP_GRID_BFS == AS_BFS, "planner codes");
+  return as_plan(ctx, planner, B, nx, ny, bound, start_real, goal_real, obs_kind, n_obs, obstacles,
+                 planner == MP_GRID_BFS ? nullptr : final_cost, found, pops, n_nodes, pop_seq, path, path_n, path_length,
+                 MP_GRID_MAX_CELLS, (flags & MP_GRID_FORCE_GLOBAL) != 0);
 }
 
 int mp_ha_astar_table(mp_ctx* ctx, const mp_ha_params* p, int32_t B, const double* goal, const double* walls,

@@ -129,6 +129,7 @@ enum {
   WS_RRT_UNI,     // ... uniforms
   WS_RRT_TREE,    // ... tree state (48 bytes per node and scene; rrtnh.hip 64)
   WS_RRT_OUT,     // ... per-scene results and paths
+  WS_GB_NODE,     // large grids (gridbig.hip): the searches' node tables, 32 bytes per cell (BFS 12)
   WS_COUNT
 };
 

@@ -2,8 +2,10 @@
 C-ABI (mp_dka_plan).
 
 ``defineDKA`` / ``defineDKAobs_`` / ``planDKA_`` keep the reference's names and argument meaning.  The search runs
-in the library, one wavefront per search (planAstar!'s kernel without the heuristic); ``plan_batch`` runs B
-searches that share the grid size in one call, whatever their obstacle counts.
+in the library (planAstar!'s kernels without the heuristic): one wavefront per search up to 51 x 51 cells, one
+workgroup on node tables in device memory above that (mp_grid_plan), and for a searcher that carries an occupancy
+mask (``defineDKAmask_``); ``plan_batch`` runs B searches that share the grid size in one call, whatever their
+obstacle counts.
 """
 from dataclasses import dataclass, field
 
@@ -25,6 +27,7 @@ class DKASettings:
     obstacle_list: list = field(default_factory=list)
     x_factor: float = 0.0
     y_factor: float = 0.0
+    free_mask: np.ndarray = None  # defineDKAmask_ (not in the reference): replaces obstacle_list
 
 
 @dataclass
@@ -57,6 +60,12 @@ def defineDKA(realsize=(-50, 0, 50, 100), mapbound=(51, 51), starting_real=(-3, 
 def defineDKAobs_(dka, obstacle_list):
     """defineDKAobs! (setup.jl:28-31): circles [x, y, r]."""
     dka.s.obstacle_list = [list(map(float, o)) for o in obstacle_list]
+    dka.s.free_mask = None
+
+
+def defineDKAmask_(dka, mask):
+    """An occupancy grid in place of the obstacle list: uint8 [ny, nx], nonzero = free (_gridsearch.define_mask)."""
+    _gridsearch.define_mask(dka, mask)
 
 
 def TransferCoordinate(dka, pos):
@@ -66,7 +75,7 @@ def TransferCoordinate(dka, pos):
 
 def plan_batch(searchers, ctx=None):
     """planDKA! for B searchers sharing mapbound; shorter obstacle lists are padded with [0, 0, 0] circles."""
-    return _gridsearch.plan_batch(searchers, "mp_dka_plan", "dkapath", True, ctx=ctx)
+    return _gridsearch.plan_batch(searchers, "dka", "dkapath", ctx=ctx)
 
 
 def planDKA_(dka, ctx=None):
