@@ -668,6 +668,69 @@ int mp_ha_track(mp_ctx* ctx, const mp_track_params* p, int32_t B, const double* 
                 int32_t* status, double* final_state, double* err_acc, double* ref_out, double* his,
                 int32_t his_cap);
 
+/* -------------------------------------------------- collision detection */
+/* PathPlanning/CollisionDetection/src/utils.jl (GetRectanglePts, Block2Pts, SeparatingAxisTheorem,
+ * ConvexCollision) and Hybrid A*'s block_collision_check (hybrid_astar_utils.jl:180-204) as batched calls.
+ * Every product is rounded as the reference's BLAS rounds it: R*pts of GetRectanglePts is dgemm with K = 2,
+ * fma(a1, b1, a0*b0); the projections transpose(pts .- bg_pt)*normal_vec are dgemv 'T' on two rows,
+ * fma(p_x - bg_x, n_x, (p_y - bg_y)*n_y).  Results are bit for bit the reference's. */
+#define MP_COLLIDE_MAX_COLS 32   /* columns (vertices incl. a closing one) per polygon */
+#define MP_SAT_BOTH   0          /* ConvexCollision, utils.jl:64-74: SAT(a,b) && SAT(b,a)          */
+#define MP_SAT_EITHER 1          /* extension: SAT(a,b) || SAT(b,a), the geometric test            */
+#define MP_SAT_BASE_A 2          /* SeparatingAxisTheorem(a, b) alone, utils.jl:37-62              */
+
+typedef struct mp_collide_params {
+  double half_len, half_wid;   /* vehicle_size[1]/2, vehicle_size[2]/2                              */
+  double center_shift;         /* pose point -> rectangle centre along the heading; reference: half_len */
+  int32_t stride;              /* sparcity_num; reference 5; >= 1                                   */
+  int32_t mode;                /* MP_SAT_*                                                          */
+} mp_collide_params;
+/* Alias of mp_collide_params, the name mp_path_collision's prototype uses; the two are one type. */
+typedef mp_collide_params mp_collide_params_t;
+
+/* GetRectanglePts (utils.jl:14-25) of n blocks [x, y, ψ, l, w]: pts[n][5][2], Julia's 2x5 matrix per block
+ * (UpLeft, LowerLeft, LowerRight, UpperRight, UpLeft again); Block2Pts is the same over a list.  A non-finite
+ * block value returns MP_ERR_INVALID; n = 0 returns MP_OK. */
+int mp_block_pts(mp_ctx* ctx, int64_t n, const double* blocks, double* pts);
+
+/* ConvexCollision / SeparatingAxisTheorem for every pair (a_i, b_j) of B scenes:
+ *   polys_a[B][na][ma][2], polys_b[B][nb][mb][2]: a polygon is its column list as given (a Julia 2 x cols
+ *   matrix); a_cols[B][na] / b_cols[B][nb] are the column counts (NULL: ma / mb each), 2 <= cols <=
+ *   min(ma or mb, MP_COLLIDE_MAX_COLS); rows past cols are padding and are never read.
+ *   SeparatingAxisTheorem(base, other) walks the cols - 1 edges between consecutive columns of base and
+ *   projects all columns of both polygons on each edge normal (-v_y, v_x); the caller closes a polygon by
+ *   repeating its first point, as the reference does.  An edge separates when
+ *   max_other <= min_base || max_base <= min_other; the first separating edge ends the walk.
+ * out: free_[B][na][nb] = 1 where the function selected by mode returns true (no collision).
+ * As in the reference, two shapes that touch are separated, and a zero-length edge (a repeated vertex) has a
+ * zero normal and separates anything.  minimum / maximum are Julia's: a NaN projection (from an overflow)
+ * makes neither comparison of its edge hold.
+ * MP_ERR_INVALID, with nothing written: a non-finite value in a row that is read, cols out of range, an
+ * unknown mode, a negative size.  B = 0 or na*nb = 0 returns MP_OK. */
+int mp_convex_collision(mp_ctx* ctx, int32_t mode, int32_t B, int32_t na, int32_t ma, const double* polys_a,
+                        const int32_t* a_cols, int32_t nb, int32_t mb, const double* polys_b, const int32_t* b_cols,
+                        uint8_t* free_);
+
+/* block_collision_check (hybrid_astar_utils.jl:180-204) for B scenes:
+ *   poses[B][n_poses][3] ([x, y, ψ]), pose_count[B] (NULL: n_poses each) poses of scene b that count,
+ *   walls[B][n_walls][5] ([x, y, ψ, l/2, w/2]), wall_count[B] (NULL: n_walls each); rows past a count are
+ *   padding and are never read.
+ * With cnt = pose_count[b]: cnt > stride checks poses 0, stride, 2 stride, ... below cnt; otherwise pose 0
+ * alone (the reference's else branch); cnt = 0 checks nothing.  A checked pose becomes the block
+ * [x + center_shift cos ψ, y + center_shift sin ψ, modπ(ψ), half_len, half_wid] and is tested against every
+ * wall of its scene as (a, b) = (wall, vehicle) under p->mode.  n_walls = 0: every scene is free.
+ * out: scene_free[B]  the reference's return value (1 = no checked pose hits a wall),
+ *      first_pose[B]  the lowest checked pose index that hits a wall, -1 if none,
+ *      first_wall[B]  the lowest wall index that pose hits, -1 if none,
+ *      n_hit[B]       checked poses that hit at least one wall,
+ *      pose_free[B][n_poses] (optional, NULL to skip): 1 free, 0 hit, 2 not checked.
+ * MP_ERR_INVALID, with nothing written: a non-finite value in a checked pose, a counted wall or the
+ * settings, a count outside its range, stride < 1, an unknown mode, a negative size.  B = 0 returns MP_OK. */
+int mp_path_collision(mp_ctx* ctx, const mp_collide_params_t* p, int32_t B, int32_t n_poses, const double* poses,
+                      const int32_t* pose_count, int32_t n_walls, const int32_t* wall_count, const double* walls,
+                      uint8_t* scene_free, int32_t* first_pose, int32_t* first_wall, int32_t* n_hit,
+                      uint8_t* pose_free);
+
 /* ---------------------------------------------------------- diagnostics */
 /* Evaluate one include/mp_jlmath.h function on the device for n inputs
  * (bit-exactness check against the CPU build).  fn: 0 sin, 1 cos, 2 tan, 3 atan,

@@ -805,6 +805,72 @@ function ha_allpath(ns::Matrix{Float64})
     return best .+ 1, cost, cmds
 end
 
+# ------------------------------------------------------ collision detection
+const MP_SAT_BOTH = Int32(0)     # ConvexCollision: SAT(a, b) && SAT(b, a)
+const MP_SAT_EITHER = Int32(1)   # SAT(a, b) || SAT(b, a)
+const MP_SAT_BASE_A = Int32(2)   # SeparatingAxisTheorem(a, b) alone
+
+struct CollideParams    # mp_collide_params (hybrid_astar_utils.jl:180-204)
+    half_len::Float64
+    half_wid::Float64
+    center_shift::Float64
+    stride::Int32
+    mode::Int32
+end
+
+"""GetRectanglePts / Block2Pts (CollisionDetection/src/utils.jl:14-34) for blocks (5, n): pts (2, 5, n)."""
+function block_pts(blocks::Matrix{Float64})
+    n = size(blocks, 2); pts = zeros(2, 5, n)
+    c = ctx()
+    check(GC.@preserve blocks pts ccall((:mp_block_pts, libmpgpu), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}), c, n, blocks, pts), c)
+    return pts
+end
+
+"""
+    convex_collision(polys_a, polys_b; a_cols = nothing, b_cols = nothing, mode = MP_SAT_BOTH)
+
+ConvexCollision (utils.jl:64-74) for every pair of polys_a (2, ma, na, B) and polys_b (2, mb, nb, B); a_cols (na, B)
+and b_cols (nb, B) give each polygon's column count (nothing: all ma / mb columns).  Returns free (nb, na, B),
+1 where the reference returns true.
+"""
+function convex_collision(polys_a::Array{Float64,4}, polys_b::Array{Float64,4}; a_cols = nothing, b_cols = nothing,
+                          mode = MP_SAT_BOTH)
+    _, ma, na, B = size(polys_a); _, mb, nb, _ = size(polys_b)
+    ac = a_cols === nothing ? Int32[] : Matrix{Int32}(a_cols)
+    bc = b_cols === nothing ? Int32[] : Matrix{Int32}(b_cols)
+    fr = zeros(UInt8, nb, na, B)
+    c = ctx()
+    check(GC.@preserve polys_a polys_b ac bc fr ccall((:mp_convex_collision, libmpgpu), Cint,
+        (Ptr{Cvoid}, Int32, Int32, Int32, Int32, Ptr{Float64}, Ptr{Int32}, Int32, Int32, Ptr{Float64}, Ptr{Int32},
+         Ptr{UInt8}),
+        c, mode, B, na, ma, polys_a, a_cols === nothing ? C_NULL : pointer(ac), nb, mb, polys_b,
+        b_cols === nothing ? C_NULL : pointer(bc), fr), c)
+    return fr
+end
+
+"""
+    path_collision(p, poses, walls; pose_count = nothing, wall_count = nothing)
+
+block_collision_check (hybrid_astar_utils.jl:180-204) for B scenes (mp_path_collision): poses (3, n_poses, B),
+walls (5, n_walls, B), with `pose_count[b]` / `wall_count[b]` of them counting (nothing: all).  Returns scene_free,
+first_pose and first_wall (0-based, -1: none), n_hit and pose_free (n_poses, B): 1 free, 0 hit, 2 not checked.
+"""
+function path_collision(p::CollideParams, poses::Array{Float64,3}, walls::Array{Float64,3}; pose_count = nothing,
+                        wall_count = nothing)
+    _, np_, B = size(poses); nw = size(walls, 2)
+    pc = pose_count === nothing ? Int32[] : Vector{Int32}(pose_count)
+    wc = wall_count === nothing ? Int32[] : Vector{Int32}(wall_count)
+    sf = zeros(UInt8, B); fp = zeros(Int32, B); fw = zeros(Int32, B); nh = zeros(Int32, B); pf = zeros(UInt8, np_, B)
+    c = ctx()
+    check(GC.@preserve poses walls pc wc sf fp fw nh pf ccall((:mp_path_collision, libmpgpu), Cint,
+        (Ptr{Cvoid}, Ref{CollideParams}, Int32, Int32, Ptr{Float64}, Ptr{Int32}, Int32, Ptr{Int32}, Ptr{Float64},
+         Ptr{UInt8}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{UInt8}),
+        c, p, B, np_, poses, pose_count === nothing ? C_NULL : pointer(pc), nw,
+        wall_count === nothing ? C_NULL : pointer(wc), walls, sf, fp, fw, nh, pf), c)
+    return (; scene_free = sf, first_pose = fp, first_wall = fw, n_hit = nh, pose_free = pf)
+end
+
 # --------------------------------------------------------------------- iLQR
 struct IlqrParams
     N::Int32

@@ -1,0 +1,1 @@
+from . import collision  # noqa: F401

@@ -154,6 +154,24 @@ class RRTParams(ctypes.Structure):
 
 MP_RRT_MAX_ITER = 1000000
 
+
+class CollideParams(ctypes.Structure):
+    """mp_collide_params (include/mpgpu.h) — block_collision_check, HybridAstar/src/hybrid_astar_utils.jl:180-204."""
+
+    _fields_ = [
+        ("half_len", ctypes.c_double),
+        ("half_wid", ctypes.c_double),
+        ("center_shift", ctypes.c_double),
+        ("stride", ctypes.c_int32),
+        ("mode", ctypes.c_int32),
+    ]
+
+
+MP_COLLIDE_MAX_COLS = 32
+MP_SAT_BOTH = 0
+MP_SAT_EITHER = 1
+MP_SAT_BASE_A = 2
+
 MP_TRACK_DONE = 0
 MP_TRACK_MAXSTEP = 1
 MP_TRACK_NOPATH = 2
@@ -206,6 +224,9 @@ SIGNATURES = {
     "mp_rrtnh_plan": (ctypes.c_int, [_V, ctypes.POINTER(RRTParams), _I, _V, _V, _V, _I] + [_V] * 13),
     "mp_ha_retrieve_path": (ctypes.c_int, [_V, _I, _V, _V, _V, _I] + [_V] * 8),
     "mp_ha_track": (ctypes.c_int, [_V, ctypes.POINTER(TrackParams), _I, _V, _V, _V, _I] + [_V] * 6 + [_I]),
+    "mp_block_pts": (ctypes.c_int, [_V, ctypes.c_int64, _V, _V]),
+    "mp_convex_collision": (ctypes.c_int, [_V, _I, _I, _I, _I, _V, _V, _I, _I, _V, _V, _V]),
+    "mp_path_collision": (ctypes.c_int, [_V, ctypes.POINTER(CollideParams), _I, _I, _V, _V, _I] + [_V] * 7),
     "mp_math_eval": (ctypes.c_int, [_V, _I, ctypes.c_int64, _V, _V, _V]),
     "mp_comm_init": (ctypes.c_int, [_V, _I]),
     "mp_comm_destroy": (ctypes.c_int, [_V, _I]),
