@@ -101,9 +101,19 @@ struct PlanArgs {
 #define MPPI_NT_CTRL 0
 #endif
 
+// The occupancy grid's LDS image (staged 16 bytes per lane) starts at the first 16-byte line of its region plus
+// the scene's offset within a line of the caller's buffer: up to 15 + 15 bytes into the region.
+constexpr int kGridPad = 32;
+typedef unsigned mp_v4u __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) mp_v4u mp_lds_v4u;
+typedef __attribute__((address_space(3))) const unsigned long long mp_lds_cu64;
+
 // Snapshot record of one scene for the deferred final rollout (final_stream = 1), in doubles:
 // [0, 2H) MPPICtrl | [2H, 4H) U_nom | X0[7] | goal[2] | obstacles[3 n_obs] | grid bytes | ran
-// `ran` (1.0 / 0.0) is written by the plan kernel of the same call: whether it planned the scene.
+// `ran` is written by the plan kernel of the same call: 0.0 when it skipped the scene, else 1.0 + g, the grid
+// starting g = 0..7 bytes into its region (the scene's offset within 8 bytes of the caller's buffer: the LDS
+// image and the record's copy then align together and the snapshot moves 8 bytes per lane; the region has one
+// spare double for it).
 // The final rollout reads it, not the closed loop's live flags, which the plant kernel on the
 // context stream may already have cleared for a later replan when the side stream gets there.
 struct FinRec {
@@ -115,7 +125,7 @@ struct FinRec {
     goal = x0 + 7;
     obs = goal + 2;
     grid = obs + 3 * n_obs;
-    ran = grid + (gbytes + 7) / 8;
+    ran = grid + (gbytes + 7) / 8 + 1;
     stride = (ran + 2) & ~1;
   }
 };
@@ -251,8 +261,25 @@ __global__ __launch_bounds__(BT) void mppi_plan_kernel(MppiDev P, PlanArgs A) {
       const int gb = P.gnx * P.gny;
       const unsigned char* gg = A.grid + (size_t)gb * s;
       if (LEAN || A.lds_grid >= 0) {
-        unsigned char* lg = reinterpret_cast<unsigned char*>(dyn + A.lds_grid);
-        for (int i = tid; i < gb; i += NT) lg[i] = gg[i];
+        // 16 bytes per lane (global_load_dwordx4 + ds_write_b128) instead of one: the LDS image starts at the
+        // scene's own offset within a 16-byte line (the region carries kGridPad spare bytes for it), so one
+        // bytewise head of (-gg) & 15 bytes aligns both sides, then the body, then a bytewise tail.  Only
+        // bytes [0, gb) of the scene are read.
+        // The image's address is formed by pointer arithmetic from dyn alone (the integers are offsets), so the
+        // rollout loop's grid lookups stay LDS reads (ds_read_u8), not flat loads whose vmcnt wait would also
+        // cover the step's collection stores.
+        const unsigned sh16 = (unsigned)(reinterpret_cast<size_t>(gg) & 15);
+        unsigned char* lb = reinterpret_cast<unsigned char*>(dyn + A.lds_grid);
+        unsigned char* lg = lb + (((0u - (unsigned)reinterpret_cast<size_t>(lb)) & 15u) + sh16);
+        const int head = min(gb, (int)((16u - sh16) & 15u)), n16 = (gb - head) >> 4;
+        const mp_v4u* g16 = reinterpret_cast<const mp_v4u*>(gg + head);
+        mp_lds_v4u* l16 = (mp_lds_v4u*)reinterpret_cast<mp_v4u*>(lg + head);
+        for (int i = tid; i < n16; i += NT) l16[i] = g16[i];
+        const int rest = gb - 16 * n16;  // head + tail bytes, fewer than 31
+        if (tid < rest) {
+          const int i = tid < head ? tid : 16 * n16 + tid;
+          lg[i] = gg[i];
+        }
         grid = lg;
       } else {
         grid = gg;
@@ -655,8 +682,26 @@ __global__ __launch_bounds__(BT) void mppi_plan_kernel(MppiDev P, PlanArgs A) {
     if (tid < 2) rec[R.goal + tid] = goal[tid];
     for (int i = tid; i < 3 * P.n_obs; i += NT) rec[R.obs + i] = obs[i];
     if (grid) {
-      unsigned char* rg = reinterpret_cast<unsigned char*>(rec + R.grid);
-      for (int i = tid; i < P.gnx * P.gny; i += NT) rg[i] = grid[i];
+      // 8 bytes per lane (ds_read_b64 + global_store_dwordx2): the copy starts g7 = the image's offset within
+      // 8 bytes into the record's region (FinRec::ran carries it), so both sides align after one bytewise head;
+      // then the body, then the tail bytes.  A grid left in HBM goes byte by byte.
+      const int gb = P.gnx * P.gny;
+      const bool wide = LEAN || A.lds_grid >= 0;
+      const int g7 = wide ? (int)(reinterpret_cast<size_t>(grid) & 7) : 0;
+      unsigned char* rg = reinterpret_cast<unsigned char*>(rec + R.grid) + g7;
+      if (tid == 0) rec[R.ran] = 1.0 + g7;
+      if (wide) {
+        const int head = min(gb, (8 - g7) & 7), n8 = (gb - head) >> 3;
+        mp_lds_cu64* s8 = (mp_lds_cu64*)reinterpret_cast<const unsigned long long*>(grid + head);
+        unsigned long long* d8 = reinterpret_cast<unsigned long long*>(rg + head);
+        for (int i = tid; i < n8; i += NT) d8[i] = s8[i];
+        if (tid < gb - 8 * n8) {  // head + tail bytes, fewer than 15
+          const int q = tid < head ? tid : 8 * n8 + tid;
+          rg[q] = grid[q];
+        }
+      } else {
+        for (int i = tid; i < gb; i += NT) rg[i] = grid[i];
+      }
     }
     MP_STAMP(5);
     return;
@@ -693,7 +738,8 @@ __global__ __launch_bounds__(64) void final_rollout_kernel(MppiDev P, const doub
   const int s = blockIdx.x, tid = threadIdx.x, side = tid & 1, H = P.H;
   const FinRec R(H, P.n_obs, P.gnx * P.gny);
   const double* rec = fin + (size_t)s * fin_stride;
-  if (rec[R.ran] == 0.0) return;  // closed loop: the plan kernel of this call skipped the scene
+  const double ran = rec[R.ran];
+  if (ran == 0.0) return;  // closed loop: the plan kernel of this call skipped the scene
   const int nw = grid_lds ? R.stride : R.grid;  // the grid stays in the record when it does not fit
   for (int i = tid; i < nw; i += 64) fsh[i] = rec[i];
   rollout_tab_fill(atab, P, threadIdx.x, blockDim.x);
@@ -705,7 +751,7 @@ __global__ __launch_bounds__(64) void final_rollout_kernel(MppiDev P, const doub
   auto ctrl = [&](int j, double* u) { u[0] = U[2 * j]; u[1] = U[2 * j + 1]; };
   auto store = [&](int, const double*) {};
   const unsigned char* grid =
-      P.gnx > 0 ? reinterpret_cast<const unsigned char*>((grid_lds ? fsh : rec) + R.grid) : nullptr;
+      P.gnx > 0 ? reinterpret_cast<const unsigned char*>((grid_lds ? fsh : rec) + R.grid) + ((int)ran - 1) : nullptr;
   const TrajOut traj{traj_out + (size_t)s * (H + 1) * 7, 7, 1};
   int f2;
   const double c2 = rollout_pair(P, fsh + R.x0, fsh + R.goal, P.n_obs > 0 ? fsh + R.obs : nullptr, grid,
@@ -1033,9 +1079,9 @@ static int plan_launch(mp_ctx* ctx, const MppiDev& D, int S, const double* X0, c
   off += 3 * D.n_obs;
   const size_t gbytes = (size_t)D.gnx * D.gny;
   A.lds_grid = -1;
-  if (D.gnx > 0 && (size_t)off * 8 + gbytes <= 48 * 1024) {
+  if (D.gnx > 0 && (size_t)off * 8 + gbytes + kGridPad <= 48 * 1024) {
     A.lds_grid = off;
-    off += (int)((gbytes + 7) / 8);
+    off += (int)((gbytes + kGridPad + 7) / 8);
   }
   // Control lists / staged partials in LDS only while two blocks still fit per CU
   // (multi-scene launches need every block co-resident); otherwise the HBM path.

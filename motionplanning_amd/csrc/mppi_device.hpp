@@ -233,27 +233,72 @@ __device__ __forceinline__ void rollout_tab_fill(double* tab, const MppiDev& P, 
   }
 }
 
-// BoundEvaluation, MPPIUtils.jl:135-151 (branch-free, same accumulation order); bnd = tab + kTabBnd
+// Select by a wave mask held on the scalar unit (a comparison's ballot): lane l gets t where bit l of m is set.
+// One v_cndmask per half straight from the mask, as mpj_sel does from its own ballot.
+__device__ __forceinline__ double sel_mask(unsigned long long m, double t, double f) {
+  unsigned rl, rh;
+  asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(rl) : "v"(__double2loint(f)), "v"(__double2loint(t)), "s"(m));
+  asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(rh) : "v"(__double2hiint(f)), "v"(__double2hiint(t)), "s"(m));
+  return __hiloint2double((int)rh, (int)rl);
+}
+
+typedef __attribute__((address_space(3))) const double* mp_lds_cdp;
+template <class T> struct is_lds_ptr { static constexpr bool value = false; };
+template <> struct is_lds_ptr<mp_lds_cdp> { static constexpr bool value = true; };
+
+// BoundEvaluation, MPPIUtils.jl:135-151 (same accumulation order); bnd = tab + kTabBnd
 // BndP: `const double*`, or the same address as an LDS pointer (bound_cost_lds).
+// Every lane of the wave calls it together (the rollout loop has no divergent path around it).
 template <class BndP>
 __device__ __forceinline__ double bound_cost(const MppiDev& P, BndP bnd, const double* x, int* ok) {
   // an opaque copy of the address: the 14 loads stay inside the step (hoisted out of the rollout loop they
   // would hold 28 VGPRs across it)
   asm volatile("" : "+v"(bnd));
-  int viol = 0;
+  // the 14 comparisons once, as wave masks on the scalar unit: below XL[i], above XU[i]
+  unsigned long long ml[7], mh[7], any = 0;
+  double bl[7], bu[7];
 #pragma unroll
-  for (int i = 0; i < 7; i++) viol |= (x[i] < bnd[2 * i]) | (x[i] > bnd[2 * i + 1]);
-  *ok &= !viol;
+  for (int i = 0; i < 7; i++) {
+    bl[i] = bnd[2 * i];
+    bu[i] = bnd[2 * i + 1];
+    ml[i] = __builtin_amdgcn_ballot_w64(x[i] < bl[i]);
+    mh[i] = __builtin_amdgcn_ballot_w64(x[i] > bu[i]);
+    any |= ml[i] | mh[i];
+  }
+  unsigned okl;  // 1 where the lane violates nothing
+  asm("v_cndmask_b32_e64 %0, 1, 0, %1" : "=v"(okl) : "s"(any));
+  *ok &= (int)okl;
   double c = 0.0;
-  if (__any(viol)) {  // wave-uniform: with no violation in the wave every lane's sum is exactly 0.0
+  if (any) {  // wave-uniform: with no violation in the wave every lane's sum is exactly 0.0
+    // Per state, again wave-uniform: a state no lane violates leaves every lane's c as it is, as the reference's
+    // selects would.  A violated state costs one addition, against the bound the lane is beyond -- the
+    // reference's single `c + slack·|x − b|`; the other lanes keep c.  Below XL and above XU at once needs
+    // XL > XU: only then (some lane with both, wave-uniform) does the reference's second addition run, for
+    // those lanes.  A NaN bound or state compares false and adds nothing, in both forms.
+    // An LDS pointer: the bounds of a violated state are read again here (opaque address, ds_read) instead of
+    // holding all 28 registers from the comparisons.  A plain pointer (the generic instances) keeps the values it
+    // compared: read again they would be flat loads, each with a vmcnt wait that also covers the step's
+    // collection stores.  slack is one scalar load per entered block, through an opaque copy (else it is
+    // fetched again, and waited for, in every state).
+    double slack = P.slack;
+    asm volatile("" : "+s"(slack));
 #pragma unroll
     for (int i = 0; i < 7; i++) {
-      const double xl = bnd[2 * i], xu = bnd[2 * i + 1];
-      const int lo = x[i] < xl, hi = x[i] > xu;
-      const double vl = c + P.slack * __builtin_fabs(x[i] - xl);
-      c = lo ? vl : c;
-      const double vh = c + P.slack * __builtin_fabs(x[i] - xu);
-      c = hi ? vh : c;
+      if (ml[i] | mh[i]) {
+        double xl = bl[i], xu = bu[i];
+        if constexpr (is_lds_ptr<BndP>::value) {
+          BndP bi = bnd + 2 * i;
+          asm volatile("" : "+v"(bi));
+          xl = bi[0];
+          xu = bi[1];
+        }
+        const double t = c + slack * __builtin_fabs(x[i] - sel_mask(ml[i], xl, xu));
+        c = sel_mask(ml[i] | mh[i], t, c);
+        if (ml[i] & mh[i]) {
+          const double vh = c + slack * __builtin_fabs(x[i] - xu);
+          c = sel_mask(ml[i] & mh[i], vh, c);
+        }
+      }
     }
   }
   return c;
@@ -262,7 +307,6 @@ __device__ __forceinline__ double bound_cost(const MppiDev& P, BndP bnd, const d
 // The same with the block addressed as LDS (the plan kernel's lean instance): behind the opaque copy a
 // plain pointer is a flat one -- flat loads, which fetch the LDS aperture back every step and whose
 // vmcnt wait also covers the step's TrajectoryCollection stores -- while an LDS pointer keeps ds_read.
-typedef __attribute__((address_space(3))) const double* mp_lds_cdp;
 __device__ __forceinline__ double bound_cost_lds(const MppiDev& P, const double* bnd, const double* x, int* ok) {
   return bound_cost(P, (mp_lds_cdp)bnd, x, ok);
 }
