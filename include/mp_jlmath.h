@@ -1517,6 +1517,9 @@ MPJ_FN void mpj_pinv2(const double* M, double* P) {
 #ifndef MPJ_PSEL /* the selects of mpj_pinv2_fast (A/B: plain ternaries) */
 #define MPJ_PSEL(c, t, f) MPJ_SEL(c, t, f)
 #endif
+#ifndef MPJ_RARE_BIT /* disjunct k of mpj_pinv2_fast's rare flag (the oracle numbers them: oracle/or_ilqr.c) */
+#define MPJ_RARE_BIT(k, c) (c)
+#endif
 /* mpj_pinv2's general path as one basic block (the device's Riccati sweep, where the branchy
  * routine's ~20 uniform branches cost more than its divisions): every operation of mpj_pinv2 on the
  * path that a generic Quu takes -- not diagonal, a21 != 0 (a real reflector, v2 != 0), a12 != 0,
@@ -1576,20 +1579,21 @@ MPJ_FN void mpj_pinv2_fast(const double* M, double* P, int* rare) {
   const double tsign = MPJ_PSEL(gbig, ts2, MPJ_PSEL(swap, ts3, ts1));
   const double dd0 = mpj_fsign(smax, tsign);
   const double dd1 = mpj_fsign(smin, tsign * mpj_fsign(1.0, f) * mpj_fsign(1.0, h));
-  *rare |= (a12 == 0.0) | (a21 == 0.0) | (v2 == 0.0) | !(__builtin_fabs(e1) > thresh) | (gbig && fa / ga < eps) |
-           (mm == 0.0);
+  *rare |= MPJ_RARE_BIT(0, a12 == 0.0) | MPJ_RARE_BIT(1, a21 == 0.0) | MPJ_RARE_BIT(2, v2 == 0.0) |
+           MPJ_RARE_BIT(3, !(__builtin_fabs(e1) > thresh)) | MPJ_RARE_BIT(4, gbig && fa / ga < eps) |
+           MPJ_RARE_BIT(5, mm == 0.0);
   /* drot on the identity */
   const double vt0 = csr * 1.0 + snr * 0.0, vt1 = csr * 0.0 + snr * 1.0;
   const double vt2 = csr * 0.0 - snr * 1.0, vt3 = csr * 1.0 - snr * 0.0;
   const double ub0 = csl * 1.0 + snl * 0.0, ub1 = csl * 0.0 - snl * 1.0;
   const double ub2 = csl * 0.0 + snl * 1.0, ub3 = csl * 1.0 - snl * 0.0;
-  *rare |= (ub1 == 0.0) & (ub3 == 0.0);
+  *rare |= MPJ_RARE_BIT(6, (ub1 == 0.0) & (ub3 == 0.0));
   /* sign fix (d >= 0) and the sort (never swaps here: |ssmin| <= |ssmax|).  The fixed values are
    * |dd0| = smax and |dd1| = smin exactly (both >= 0), so the reciprocals below start from smax and
    * smin without waiting for the sign decision. */
   const int n0 = dd0 < 0.0, n1 = dd1 < 0.0;
   const double S0 = smax, S1 = smin;
-  *rare |= !(S1 <= S0) | !(S0 > 0.0);
+  *rare |= MPJ_RARE_BIT(7, !(S1 <= S0) | !(S0 > 0.0));
   const double V0 = MPJ_PSEL(n0, vt0 * -1.0, vt0), V1 = MPJ_PSEL(n0, vt1 * -1.0, vt1);
   const double V2 = MPJ_PSEL(n1, vt2 * -1.0, vt2), V3 = MPJ_PSEL(n1, vt3 * -1.0, vt3);
   /* dormbr: U = H1 * Ub on both columns (lastv = 2, lastc = 2: column 2 of Ub is never zero) */

@@ -745,6 +745,16 @@ int mp_path_collision(mp_ctx* ctx, const mp_collide_params_t* p, int32_t B, int3
  * 1·(numerator changed) + 2·(divisor changed) + 4·(VCC set), to check the guard's window against. */
 int mp_math_eval(mp_ctx* ctx, int32_t fn, int64_t n, const double* x, const double* y, double* out);
 
+/* Evaluate the 2x2 pseudo-inverse / SVD of include/mp_jlmath.h on the device for n row-major matrices
+ * M[n][4], one thread per matrix in 256-thread blocks (bit-exactness check against the CPU build; n <= 2^24).
+ * mode 0: mpj_pinv2 (exact, branchy)            -> out[n][4] = P;
+ * mode 1: mpj_pinv2_bl (the Riccati sweep's)    -> out[n][4] = P.  Its exact fallback is taken by a whole
+ *         wave when any of its lanes is rare, so matrix i meets the matrices 64*(i/64) .. 64*(i/64) + 63;
+ * mode 2: mpj_pinv2_fast (straight-line path)   -> out[n][4] = P (meaningful where rare is 0), rare[i] = 0 / 1;
+ * mode 3: mpj_svd2                              -> out[n][10] = U[4], S[2], VT[4].
+ * rare[n] is optional (NULL to skip) and written as 0 in the modes other than 2. */
+int mp_pinv2_eval(mp_ctx* ctx, int32_t mode, int64_t n, const double* M, double* out, int32_t* rare);
+
 #ifdef __cplusplus
 }
 #endif

@@ -228,6 +228,7 @@ SIGNATURES = {
     "mp_convex_collision": (ctypes.c_int, [_V, _I, _I, _I, _I, _V, _V, _I, _I, _V, _V, _V]),
     "mp_path_collision": (ctypes.c_int, [_V, ctypes.POINTER(CollideParams), _I, _I, _V, _V, _I] + [_V] * 7),
     "mp_math_eval": (ctypes.c_int, [_V, _I, ctypes.c_int64, _V, _V, _V]),
+    "mp_pinv2_eval": (ctypes.c_int, [_V, _I, ctypes.c_int64, _V, _V, _V]),
     "mp_comm_init": (ctypes.c_int, [_V, _I]),
     "mp_comm_destroy": (ctypes.c_int, [_V, _I]),
     "mp_comm_allgather_dev": (ctypes.c_int, [_V, _I, _V, _V, ctypes.c_size_t]),

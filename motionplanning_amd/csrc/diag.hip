@@ -61,6 +61,30 @@ __global__ void math_kernel(int fn, long long n, const double* x, const double* 
   out[i] = r;
 }
 bool two_op(int fn) { return fn == 4 || fn == 18 || fn >= 25; }
+
+// One thread per row-major 2x2.  mpj_pinv2_bl's exact fallback is wave-uniform (MPJ_ANY), so what a lane
+// computes in mode 1 depends on the matrices of the other lanes of its wave; the lanes past n have left.
+__global__ __launch_bounds__(256) void pinv2_kernel(int mode, long long n, const double* M, double* out, int* rare) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double m[4] = {M[4 * i], M[4 * i + 1], M[4 * i + 2], M[4 * i + 3]};
+  if (mode == 3) {
+    double U[4], S[2], VT[4];
+    mpj_svd2(m, U, S, VT);
+    double* o = out + 10 * i;
+    for (int c = 0; c < 4; c++) { o[c] = U[c]; o[6 + c] = VT[c]; }
+    o[4] = S[0];
+    o[5] = S[1];
+    return;
+  }
+  double P[4];
+  int ra = 0;
+  if (mode == 0) mpj_pinv2(m, P);
+  else if (mode == 1) mpj_pinv2_bl(m, P);
+  else mpj_pinv2_fast(m, P, &ra);
+  for (int c = 0; c < 4; c++) out[4 * i + c] = P[c];
+  if (rare) rare[i] = mode == 2 ? (ra != 0) : 0;
+}
 }  // namespace
 
 extern "C" int mp_math_eval(mp_ctx* ctx, int32_t fn, int64_t n, const double* x, const double* y, double* out) {
@@ -77,6 +101,26 @@ extern "C" int mp_math_eval(mp_ctx* ctx, int32_t fn, int64_t n, const double* x,
                      dy, dout);
   MP_HIP(ctx, hipGetLastError());
   if ((st = mp_download(ctx, out, (const double*)dout, (size_t)n))) return st;
+  MP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return MP_OK;
+}
+
+extern "C" int mp_pinv2_eval(mp_ctx* ctx, int32_t mode, int64_t n, const double* M, double* out, int32_t* rare) {
+  if (!ctx) return MP_ERR_INVALID;
+  MP_CHECK(ctx, mode >= 0 && mode <= 3 && n >= 0 && n <= (int64_t)1 << 24 && M && out, "bad mp_pinv2_eval arguments");
+  if (n == 0) return MP_OK;
+  MP_HIP(ctx, hipSetDevice(ctx->device));
+  int st = MP_OK;
+  const size_t per = mode == 3 ? 10 : 4;
+  const double* dM = mp_upload(ctx, WS_IO0, M, 4 * (size_t)n, &st);
+  double* dout = mp_alloc_out(ctx, WS_IO1, out, per * (size_t)n, &st);
+  int* drare = mp_alloc_out(ctx, WS_IO2, (int*)rare, (size_t)n, &st);
+  if (st) return st;
+  hipLaunchKernelGGL(pinv2_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (int)mode, (long long)n,
+                     dM, dout, drare);
+  MP_HIP(ctx, hipGetLastError());
+  if ((st = mp_download(ctx, out, (const double*)dout, per * (size_t)n))) return st;
+  if ((st = mp_download(ctx, (int*)rare, (const int*)drare, (size_t)n))) return st;
   MP_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return MP_OK;
 }

@@ -65,6 +65,7 @@ def lib():
         L.or_pinv2_batch.argtypes = [ctypes.c_int, _V, _V]
         L.or_svd2_batch.argtypes = [ctypes.c_int, _V, _V, _V, _V]
         L.or_pinv2_fast_batch.argtypes = [ctypes.c_int, _V, _V, _V]
+        L.or_pinv2_fast_mask_batch.argtypes = [ctypes.c_int, _V, _V, _V]
         L.or_chol2.argtypes = [_V, _V]
         L.or_mppi_ctrl_term.restype = _D
         L.or_mppi_ctrl_term.argtypes = [_D, _V, _V, _V]
@@ -74,12 +75,14 @@ def lib():
         for name, args in [
             ("or_ilqr_rollout", [ctypes.POINTER(ILQRParams), _V, _V, _V]),
             ("or_ilqr_backward", [ctypes.POINTER(ILQRParams), _V, _V, _V, _V]),
+            ("or_ilqr_backward_quu", [ctypes.POINTER(ILQRParams), _V, _V, _V, _V, _V]),
             ("or_ilqr_forward", [ctypes.POINTER(ILQRParams), _V, _V, _V, _V, _D, _V, _V]),
             ("or_ilqr_solve", [ctypes.POINTER(ILQRParams), _V, _V, ctypes.POINTER(_D), ctypes.POINTER(_I)]),
         ]:
             if hasattr(L, name):
                 f = getattr(L, name)
-                f.restype = {"or_ilqr_solve": ctypes.c_int, "or_ilqr_backward": ctypes.c_int}.get(name, _D)
+                f.restype = {"or_ilqr_solve": ctypes.c_int, "or_ilqr_backward": ctypes.c_int,
+                             "or_ilqr_backward_quu": ctypes.c_int}.get(name, _D)
                 f.argtypes = args
         _lib = L
     return _lib
@@ -135,12 +138,18 @@ def pinv2_batch(M):
     return P
 
 
-def pinv2_fast_batch(M):
-    """mpj_pinv2_fast (the straight-line general path): (P, rare)."""
+RARE_DISJUNCTS = ("a12 == 0", "a21 == 0", "v2 == 0", "split", "gbig && fa/ga < eps", "mm == 0", "ub1 == ub3 == 0",
+                  "!(S1 <= S0) | !(S0 > 0)")  # bit i of the mask: mpj_pinv2_fast's rare expression, in its order
+
+
+def pinv2_fast_batch(M, want_mask=False):
+    """mpj_pinv2_fast (the straight-line general path): (P, rare), rare 0 / 1; want_mask: (P, rare, mask),
+    mask the disjuncts of the rare expression that hold (bit i: RARE_DISJUNCTS[i])."""
     M = np.ascontiguousarray(M, np.float64).reshape(-1, 2, 2)
-    P, rare = np.zeros_like(M), np.zeros(len(M), np.int32)
-    lib().or_pinv2_fast_batch(len(M), ptr(M), ptr(P), ptr(rare))
-    return P, rare
+    P, mask = np.zeros_like(M), np.zeros(len(M), np.int32)
+    lib().or_pinv2_fast_mask_batch(len(M), ptr(M), ptr(P), ptr(mask))
+    rare = (mask != 0).astype(np.int32)
+    return (P, rare, mask) if want_mask else (P, rare)
 
 
 def svd2_batch(A):
@@ -266,13 +275,15 @@ def ilqr_rollout(p, x0, U):
     return X, J
 
 
-def ilqr_backward(p, X, U):
+def ilqr_backward(p, X, U, want_quu=False):
+    """One backward sweep: (k, K); want_quu: (k, K, Quu), Quu (N-1, 2, 2) as each knot hands it to pinv."""
     X = np.ascontiguousarray(X, np.float64)
     U = np.ascontiguousarray(U, np.float64)
     k = np.zeros((p.N - 1, 2))
     K = np.zeros((p.N - 1, 4, 2))
-    lib().or_ilqr_backward(ctypes.byref(p), ptr(X), ptr(U), ptr(k), ptr(K))
-    return k, K
+    Quu = np.zeros((p.N - 1, 2, 2)) if want_quu else None
+    lib().or_ilqr_backward_quu(ctypes.byref(p), ptr(X), ptr(U), ptr(k), ptr(K), ptr(Quu))
+    return (k, K, Quu) if want_quu else (k, K)
 
 
 def ilqr_forward(p, X, U, k, K, alpha):

@@ -16,6 +16,9 @@
 #include <stdlib.h>
 #include <string.h>
 
+/* mpj_pinv2_fast's rare flag as a bit mask, one bit per disjunct (or_pinv2_fast_mask_batch; the device and every
+ * other translation unit keep the plain 0/1 terms) */
+#define MPJ_RARE_BIT(k, c) ((c) ? 1 << (k) : 0)
 #include "../include/mp_jlmath.h"
 #include "../include/mpgpu.h"
 #include "or_blas.h"
@@ -169,8 +172,18 @@ void or_pinv2_batch(int n, const double* M, double* P) {
 /* the device sweep's straight-line variant (mpj_pinv2_fast); rare[i] = 1 where it defers to mpj_pinv2 */
 void or_pinv2_fast_batch(int n, const double* M, double* P, int* rare) {
   for (int i = 0; i < n; i++) {
-    rare[i] = 0;
-    mpj_pinv2_fast(M + 4 * i, P + 4 * i, rare + i);
+    int m = 0;
+    mpj_pinv2_fast(M + 4 * i, P + 4 * i, &m);
+    rare[i] = m != 0;
+  }
+}
+/* the same with mask[i] = the disjuncts of its rare expression that hold, as bits 0 a12 == 0, 1 a21 == 0,
+ * 2 v2 == 0, 3 dbdsqr split, 4 dlasv2 gbig && fa/ga < eps, 5 mm == 0, 6 ub1 == ub3 == 0,
+ * 7 !(S1 <= S0) | !(S0 > 0) */
+void or_pinv2_fast_mask_batch(int n, const double* M, double* P, int* mask) {
+  for (int i = 0; i < n; i++) {
+    mask[i] = 0;
+    mpj_pinv2_fast(M + 4 * i, P + 4 * i, mask + i);
   }
 }
 void or_svd2_batch(int n, const double* A, double* U, double* S, double* VT) {
@@ -198,8 +211,10 @@ void or_pinv2_closed(const double* M, double* P) {
   P[3] = -st * i1 * sp + ct * i2 * cp;
 }
 
-/* ILQR.jl:46-67, one backward sweep.  Returns 0. */
-int or_ilqr_backward(const mp_ilqr_params* p, const double* X, const double* U, double* kout, double* Kout) {
+/* ILQR.jl:46-67, one backward sweep.  Returns 0.  QuuOut[N-1][4] (optional, NULL to skip): each knot's Quu,
+ * row-major, as handed to pinv (tests/ilqr_rare_cases.py classifies the knots from it). */
+int or_ilqr_backward_quu(const mp_ilqr_params* p, const double* X, const double* U, double* kout, double* Kout,
+                         double* QuuOut) {
   const int N = p->N;
   const double e = p->eps;
   double Vx[4], Vxx[16], lx[4], lu[2], lxx[16], luu[4], lux[8], A[16], B[8];
@@ -230,6 +245,7 @@ int or_ilqr_backward(const mp_ilqr_params* p, const double* X, const double* U, 
       for (int c = 0; c < 2; c++) Quu[2 * i + c] = luu[2 * i + c] + blk4(T24 + 4 * i, 1, B + c, 2);
     for (int i = 0; i < 2; i++)                                             /* Qux = lux + (fu' Vxx) fx */
       for (int c = 0; c < 4; c++) Qux[4 * i + c] = lux[4 * i + c] + blk4(T24 + 4 * i, 1, A + c, 4);
+    if (QuuOut) memcpy(QuuOut + 4 * j, Quu, 32);
     or_pinv2(Quu, P);
     double kk[2], KK[8];
     /* k = -pinv(Quu) * Qu, K = -pinv(Quu) * Qux: dgemm with K = 2 (2x1 and 2x4 right operands) */
@@ -251,6 +267,11 @@ int or_ilqr_backward(const mp_ilqr_params* p, const double* X, const double* U, 
       for (int c = 0; c < 4; c++) Vxx[4 * i + c] = Qxx[4 * i + c] - blk2(KQ[2 * i + 0], KK[0 * 4 + c], KQ[2 * i + 1], KK[1 * 4 + c]);
   }
   return 0;
+}
+
+/* the sweep without the Quu output (the entry point's signature is kept for its callers) */
+int or_ilqr_backward(const mp_ilqr_params* p, const double* X, const double* U, double* kout, double* Kout) {
+  return or_ilqr_backward_quu(p, X, U, kout, Kout, NULL);
 }
 
 /* ILQR.jl:72-80, one forward trial at step size alpha; returns J_new. */
