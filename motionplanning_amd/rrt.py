@@ -7,12 +7,12 @@ settings in one call (bounds, start, goal and obstacle lists may differ per tree
 random numbers: the three uniforms of every iteration are an input, drawn here with
 ``numpy.random.default_rng(seed)`` unless given.
 """
-import time
 from dataclasses import dataclass, field
 
 import numpy as np
 
-from .abi import RRTParams, f64, ptr
+from . import _rrt
+from ._rrt import defineRRTobs_  # noqa: F401  (defineRRTobs!, setup.jl:43-46: circles [x, y, r])
 from .context import default_context
 
 
@@ -78,13 +78,8 @@ def defineRRT(sampling_size=10000, starting_pose=(35.0, 50.0), ending_pose=(100.
     return rrt
 
 
-def defineRRTobs_(rrt, obstacle_list):
-    """defineRRTobs! (setup.jl:43-46): circles [x, y, r]."""
-    rrt.s.obstacle_list = [[float(v) for v in o] for o in obstacle_list]
-
-
-def _settings_key(s):
-    return (s.sampling_number, s.buffer_size, s.rrt_star, s.bias_rate, tuple(s.grow_dist), s.goal_tolerance)
+def _pack(searchers, uniforms=None):
+    return _rrt.pack_scenes(searchers, [a.s.starting_position for a in searchers], 3, uniforms)
 
 
 def plan_batch(searchers, uniforms=None, ctx=None):
@@ -92,52 +87,7 @@ def plan_batch(searchers, uniforms=None, ctx=None):
     goal_tolerance.  uniforms: [B][n_iter][3] (u_bias, u_x, u_y), or None to draw them per searcher from
     ``numpy.random.default_rng(searcher.s.seed)``."""
     ctx = ctx or default_context()
-    s0 = searchers[0].s
-    if any(_settings_key(a.s) != _settings_key(s0) for a in searchers):
-        raise ValueError("plan_batch: every searcher needs the same sampling_number, buffer_size, rrt_star, "
-                         "bias_rate, grow_dist and goal_tolerance")
-    B, n_iter = len(searchers), int(s0.sampling_number)
-    cap = n_iter + 1
-    p = RRTParams(n_iter=n_iter, buffer_size=int(s0.buffer_size), rrt_star=int(s0.rrt_star), reserved=0,
-                  bias_rate=float(s0.bias_rate), grow_min=float(s0.grow_dist[0]), grow_max=float(s0.grow_dist[1]),
-                  goal_tolerance=float(s0.goal_tolerance))
-    if uniforms is None:
-        uniforms = [np.random.default_rng(a.s.seed).random((max(n_iter, 0), 3)) for a in searchers]
-    uni = f64(uniforms).reshape(B, max(n_iter, 0), 3)
-    bound = f64([a.s.BoundPosition for a in searchers])
-    start = f64([a.s.starting_position for a in searchers])
-    goal = f64([a.s.ending_position for a in searchers])
-    # obstacle lists padded to the longest; obs_count tells the library how many rows of each count
-    count = np.array([len(a.s.obstacle_list) for a in searchers], np.int32)
-    n_obs = int(count.max())
-    obs = np.zeros((B, n_obs, 3))
-    for b, a in enumerate(searchers):
-        if count[b]:
-            obs[b, : count[b]] = f64(a.s.obstacle_list).reshape(-1, 3)
-    nn, status, best, pn = (np.zeros(B, np.int32) for _ in range(4))
-    bcost = np.zeros(B)
-    loc, cost = np.zeros((B, max(cap, 1), 2)), np.zeros((B, max(cap, 1)))
-    parent, path = np.zeros((B, max(cap, 1)), np.int32), np.zeros((B, max(cap, 1)), np.int32)
-    counters = np.zeros((B, 4), np.int32)
-    t0 = time.time()
-    ctx.check(ctx.lib.mp_rrt_plan(ctx.handle, p, B, ptr(bound), ptr(start), ptr(goal), n_obs, ptr(count),
-                                  ptr(obs) if n_obs else None, ptr(uni), ptr(nn), ptr(status), ptr(best), ptr(bcost),
-                                  ptr(loc), ptr(cost), ptr(parent), ptr(path), ptr(pn), ptr(counters)))
-    dt = time.time() - t0
-    for b, a in enumerate(searchers):
-        r = a.r = RRTResult()
-        r.n_nodes = int(nn[b])
-        r.loc, r.costs, r.parents = loc[b, : nn[b]].copy(), cost[b, : nn[b]].copy(), parent[b, : nn[b]].copy()
-        r.counters = counters[b].copy()
-        r.tSolve = dt
-        if status[b]:
-            r.status = "Solved"
-            r.resultIdxs = path[b, : pn[b]].astype(np.int64)
-            r.Path = r.loc[r.resultIdxs - 1].T.copy()  # getBestPath (rrt_utils.jl:424-431): 2 x k
-            r.cost = float(bcost[b])
-        else:
-            r.status = "NotSolved"
-    return searchers
+    return _rrt.run(ctx, ctx.lib.mp_rrt_plan, _pack(searchers, uniforms), searchers, RRTResult, "loc", 4)
 
 
 def planRRT_(rrt, ctx=None):

@@ -8,12 +8,12 @@ draws no random numbers: the six uniforms of every iteration (u_bias, u_x, u_y, 
 input, drawn here with ``numpy.random.default_rng(seed)`` unless given.  The terrain, candidacy and TPP parts of
 the reference are never reached from planRRT! and have no counterpart.
 """
-import time
 from dataclasses import dataclass, field
 
 import numpy as np
 
-from .abi import RRTParams, f64, ptr
+from . import _rrt
+from ._rrt import defineRRTobs_  # noqa: F401  (defineRRTobs!, setup.jl:41-44: circles [x, y, r])
 from .context import default_context
 
 
@@ -86,13 +86,8 @@ def defineRRT(sampleNum=10000, starting_pose=(35.0, 50.0), starting_ang=0.0, end
     return rrt
 
 
-def defineRRTobs_(rrt, obstacle_list):
-    """defineRRTobs! (setup.jl:41-44): circles [x, y, r]."""
-    rrt.s.obstacle_list = [[float(v) for v in o] for o in obstacle_list]
-
-
-def _settings_key(s):
-    return (s.sampling_number, s.buffer_size, s.rrt_star, s.bias_rate, tuple(s.grow_dist), s.goal_tolerance)
+def _pack(searchers, uniforms=None):
+    return _rrt.pack_scenes(searchers, [[*a.s.starting_position, a.s.starting_ang] for a in searchers], 6, uniforms)
 
 
 def plan_batch(searchers, ctx=None, uniforms=None):
@@ -100,54 +95,7 @@ def plan_batch(searchers, ctx=None, uniforms=None):
     goal_tolerance.  uniforms: [B][n_iter][6] (u_bias, u_x, u_y, u_psi, u_ratio, u_yaw), or None to draw them per
     searcher from ``numpy.random.default_rng(searcher.s.seed)``."""
     ctx = ctx or default_context()
-    s0 = searchers[0].s
-    if any(_settings_key(a.s) != _settings_key(s0) for a in searchers):
-        raise ValueError("plan_batch: every searcher needs the same sampling_number, buffer_size, rrt_star, "
-                         "bias_rate, grow_dist and goal_tolerance")
-    B, n_iter = len(searchers), int(s0.sampling_number)
-    cap = n_iter + 1
-    p = RRTParams(n_iter=n_iter, buffer_size=int(s0.buffer_size), rrt_star=int(s0.rrt_star), reserved=0,
-                  bias_rate=float(s0.bias_rate), grow_min=float(s0.grow_dist[0]), grow_max=float(s0.grow_dist[1]),
-                  goal_tolerance=float(s0.goal_tolerance))
-    if uniforms is None:
-        uniforms = [np.random.default_rng(a.s.seed).random((max(n_iter, 0), 6)) for a in searchers]
-    uni = f64(uniforms).reshape(B, max(n_iter, 0), 6)
-    bound = f64([a.s.BoundPosition for a in searchers])
-    start = f64([[a.s.starting_position[0], a.s.starting_position[1], a.s.starting_ang] for a in searchers])
-    goal = f64([a.s.ending_position for a in searchers])
-    # obstacle lists padded to the longest; obs_count tells the library how many rows of each count
-    count = np.array([len(a.s.obstacle_list) for a in searchers], np.int32)
-    n_obs = int(count.max())
-    obs = np.zeros((B, n_obs, 3))
-    for b, a in enumerate(searchers):
-        if count[b]:
-            obs[b, : count[b]] = f64(a.s.obstacle_list).reshape(-1, 3)
-    nn, status, best, pn = (np.zeros(B, np.int32) for _ in range(4))
-    bcost = np.zeros(B)
-    state, cost = np.zeros((B, max(cap, 1), 3)), np.zeros((B, max(cap, 1)))
-    parent, path = np.zeros((B, max(cap, 1)), np.int32), np.zeros((B, max(cap, 1)), np.int32)
-    counters = np.zeros((B, 8), np.int32)
-    t0 = time.time()
-    ctx.check(ctx.lib.mp_rrtnh_plan(ctx.handle, p, B, ptr(bound), ptr(start), ptr(goal), n_obs, ptr(count),
-                                    ptr(obs) if n_obs else None, ptr(uni), ptr(nn), ptr(status), ptr(best),
-                                    ptr(bcost), ptr(state), ptr(cost), ptr(parent), ptr(path), ptr(pn),
-                                    ptr(counters)))
-    dt = time.time() - t0
-    for b, a in enumerate(searchers):
-        r = a.r = RRTResult()
-        r.n_nodes = int(nn[b])
-        r.states = state[b, : nn[b]].copy()
-        r.costs, r.parents = cost[b, : nn[b]].copy(), parent[b, : nn[b]].copy()
-        r.counters = counters[b].copy()
-        r.tSolve = dt
-        if status[b]:
-            r.status = "Solved"
-            r.resultIdxs = path[b, : pn[b]].astype(np.int64)
-            r.Path = r.states[r.resultIdxs - 1, :2].T.copy()  # getBestPath (rrt_utils.jl:595-602): 2 x k
-            r.cost = float(bcost[b])
-        else:
-            r.status = "NotSolved"
-    return searchers
+    return _rrt.run(ctx, ctx.lib.mp_rrtnh_plan, _pack(searchers, uniforms), searchers, RRTResult, "states", 8)
 
 
 def planRRT_(rrt, ctx=None, uniforms=None):
