@@ -378,24 +378,13 @@ __device__ __forceinline__ void wall_cull(const HaDev& P, const double* wp, cons
   }
   cl[2] = mpj_sqrt(r2) * (1 + 1e-12) + 1e-6;
 }
-// (A/B) -DHA_SAT_OVERLAP=1 enables class 2 below (proved in the oracle test; not yet measured on the GPU)
-#ifndef HA_SAT_OVERLAP
-#define HA_SAT_OVERLAP 0
-#endif
 // Wall-side class of a vehicle centred at (x, y), from its projections on the wall's edge normals 0, 1:
 //  1: SAT(wall, vehicle) is certainly true (wall_cull's cl[0..1]);
-//  2: the centre lies inside the wall, at least 1e-5 of the wall's extent from each side along both
-//     normals: the centre is then interior to both rectangles by far more than any rounding error, so
-//     on every axis the two projections overlap and both SeparatingAxisTheorem calls return false --
-//     the pose collides (tests/test_oracle_hastar.py);
-//  0: neither is certain.
+//  0: it is not certain.
 __device__ __forceinline__ int wall_side_class(const double* pre, const double* cl, double x, double y) {
   const double d0 = (x - pre[0]) * pre[2] + (y - pre[1]) * pre[3];
   const double d1 = (x - pre[6]) * pre[8] + (y - pre[7]) * pre[9];
-  if ((d0 - cl[0] > pre[5]) | (d0 + cl[0] < pre[4]) | (d1 - cl[1] > pre[11]) | (d1 + cl[1] < pre[10])) return 1;
-  if (!HA_SAT_OVERLAP) return 0;
-  const double m0 = (pre[5] - pre[4]) * 1e-5, m1 = (pre[11] - pre[10]) * 1e-5;
-  return ((d0 > pre[4] + m0) & (d0 < pre[5] - m0) & (d1 > pre[10] + m1) & (d1 < pre[11] - m1)) ? 2 : 0;
+  return (d0 - cl[0] > pre[5]) | (d0 + cl[0] < pre[4]) | (d1 - cl[1] > pre[11]) | (d1 + cl[1] < pre[10]);
 }
 // 1: SAT(vehicle, wall) is certainly true; (dx, dy) = vehicle centre - wall centre, (cy, sy) the
 // vehicle rectangle's heading (wall_cull's cl[2])
@@ -435,9 +424,6 @@ __device__ __forceinline__ int pose_free_t(const HaDev& P, const double* q, cons
     const double dx = x - wc[3 * i], dy = y - wc[3 * i + 1];
     if (dx * dx + dy * dy > wc[3 * i + 2]) continue;  // far from this wall: separated for certain
     const int ws = wall_side_class(wpre + 24 * i, wcl + 3 * i, x, y);
-#if HA_SAT_OVERLAP
-    if (ws == 2) return 0;  // centre inside the wall: collides for certain
-#endif
     need |= (unsigned)(ws != 1) << (2 * i);
     need |= (unsigned)!cull_vehicle_side(P, wcl + 3 * i, dx, dy, cy, sy) << (2 * i + 1);
   }
@@ -464,13 +450,7 @@ __device__ __forceinline__ int pose_free_part(const HaDev& P, const double* q, c
   const double x = q[0] + P.L2 * cq, y = q[1] + P.L2 * sq;
   const double fx = x - wc[3 * w], fy = y - wc[3 * w + 1];
   if (fx * fx + fy * fy > wc[3 * w + 2]) return 1;  // far from this wall: separated for certain
-#if HA_SAT_OVERLAP
-  const int ws = wall_side_class(wpre + 24 * w, wcl + 3 * w, x, y);
-  if (ws == 2) return 0;  // centre inside the wall: both terms are false
-  if (d == 0 && ws == 1) return 1;
-#else
   if (d == 0 && wall_side_class(wpre + 24 * w, wcl + 3 * w, x, y) == 1) return 1;
-#endif
   const double yaw = mpj_modpi_bl(q[2]);
   double sy = sq, cy = cq;
   if (MPJ_ANY(yaw != q[2])) mpj_sincos_bl(yaw, &sy, &cy);
@@ -485,13 +465,7 @@ __device__ __forceinline__ int pose_free_part_t(const HaDev& P, const double* q,
   const double x = q[0] + P.L2 * T.cq, y = q[1] + P.L2 * T.sq;
   const double fx = x - wc[3 * w], fy = y - wc[3 * w + 1];
   if (fx * fx + fy * fy > wc[3 * w + 2]) return 1;
-#if HA_SAT_OVERLAP
-  const int ws = wall_side_class(wpre + 24 * w, wcl + 3 * w, x, y);
-  if (ws == 2) return 0;
-  if (d == 0 && ws == 1) return 1;
-#else
   if (d == 0 && wall_side_class(wpre + 24 * w, wcl + 3 * w, x, y) == 1) return 1;
-#endif
   if (d == 1 && cull_vehicle_side(P, wcl + 3 * w, fx, fy, T.cy, T.sy)) return 1;
   double vp[10];
   rect_pts(x, y, T.cy, T.sy, P.L2, P.W2, vp);
@@ -702,7 +676,7 @@ __device__ __forceinline__ int wait_ge(const int* p, int v, int* err) {
 // own lane, so the bookkeeping neither drains its stores nor raises a separate flag, and a consumer wave polls
 // the 14 words until every tag matches (one round trip instead of flag + node).  HA_NGR_DONE in the go word's
 // tag: the scene's search ended.  The go word's value: bit 0 go (a node follows), bit 1 skip (the consumer has
-// nothing to do this round: the node's expansion was made speculatively, or no runner-up exists; HA_SPEC).
+// nothing to do this round: the node's expansion was made speculatively, or no runner-up exists; SPEC).
 constexpr int HA_NGR = 16;
 // granule slots by iteration (it & 7): a slot is rewritten by the bookkeeping seven iterations on -- its consumers
 // (the expansion groups, and one of the scene's two RS_connected blocks) take it as soon as it appears and run at
@@ -775,15 +749,11 @@ __device__ __forceinline__ OutRef out_ref(const IterArgs& A, int s, int n_prim) 
   return r;
 }
 
-// threads per block of ha_iter_kernel: 4 waves, three Reeds–Shepp words per wave (HA_WAVES=6 or 12:
+// threads per block of ha_iter_kernel: 4 waves, three Reeds–Shepp words per wave (6 or 12 waves,
 // two words or one per wave: measured slower, 55 / 53 ms vs 45 ms per 256-scenario plan -- the
 // per-wave Reeds–Shepp set-up is repeated and the launch is already issue-bound).
-#ifndef HA_WAVES
-#define HA_WAVES 4
-#endif
-constexpr int HW = HA_WAVES;
+constexpr int HW = 4;
 constexpr int HT = 64 * HW;
-static_assert(12 % HW == 0, "HA_WAVES must divide the 12 Reeds-Shepp words");
 // Tail shape, for iterations with few scenes still searching (the latency-bound end of a batched
 // plan): 12 waves per block (one Reeds-Shepp word per wave) and 4 neighbours per expansion block
 // (16 blocks per scene: the collision sweep is one pose per thread), so a lone scene's iteration
@@ -793,22 +763,14 @@ static_assert(12 % HW == 0, "HA_WAVES must divide the 12 Reeds-Shepp words");
 #ifndef HA_STAMP_CODE
 #define HA_STAMP_CODE 0
 #endif
-#ifndef HA_NBG_TAIL
-#define HA_NBG_TAIL 4
-#endif
-constexpr int HW_TAIL = 12, NBG_TAIL = HA_NBG_TAIL;
-// the middle shape's waves per block (HA_MID_BLOCKS): 16 neighbours each, 12 / HA_MID_HW Reeds-Shepp
-// words per wave (12-wave blocks measured 38 ms per 256-plan at MID 1024, r05q; 6-wave ones 24.9, r05x)
-#ifndef HA_MID_HW
-#define HA_MID_HW 6
-#endif
-// the tail shape's rs_heuristic in word units spread over the scene's groups (ha_iter_body RSH); 0, or a
-// primitive count that does not tile: the groups' own word search after their sweep.  (The groups' own search
-// for all their neighbours overlapped with the sweep measured slower on the lone 729-pop scenario, 29.1 vs
-// 28.3 us per iteration, profiles/r05e_ha_lone_block_stamps_overlap.txt.)
-#ifndef HA_TAIL_RSH
-#define HA_TAIL_RSH 1
-#endif
+constexpr int HW_TAIL = 12, NBG_TAIL = 4;
+// the middle shape's waves per block: 16 neighbours each, 2 Reeds-Shepp words per wave
+// (12-wave blocks measured 38 ms per 256-plan at a 1024-block threshold, r05q; 6-wave ones 24.9, r05x)
+constexpr int HW_MID = 6;
+// The tail shape's rs_heuristic runs in word units spread over the scene's groups (ha_iter_body RSH) when
+// the primitive count tiles; otherwise the groups search their own words after their sweep.  (The groups' own
+// search for all their neighbours overlapped with the sweep measured slower on the lone 729-pop scenario,
+// 29.1 vs 28.3 us per iteration, profiles/r05e_ha_lone_block_stamps_overlap.txt.)
 
 // allpath + findmin split over the block's HW waves: wave w evaluates words WPW·w+1..WPW·(w+1) for
 // its lanes' candidates (lane&3 = variant of the state in `s`), the per-wave winners are
@@ -1023,7 +985,7 @@ __device__ __forceinline__ bool ha_iter_body(const HaDev& P, const IterArgs& A, 
       }
       __syncthreads();
       if (!nd_go) return false;  // block-uniform: the search ended, nothing to expand
-      if (nd_go & 2) return true;  // block-uniform: nothing to do this round (HA_SPEC: expanded speculatively)
+      if (nd_go & 2) return true;  // block-uniform: nothing to do this round (SPEC: expanded speculatively)
     } else {
       if (tid == 0) nd_go = wait_ge(A.node_flag + s, A.node_flag_min, A.node_flag_err) & 1;
       __syncthreads();
@@ -1580,7 +1542,7 @@ struct HaSearch {
   int* ex;               // [B] (ha_persist_kernel) expansions finished (neighbour groups, cumulative)
   int* rsr;              // [2][B] (ha_persist_kernel) 2·it + 2 once RS_connected(n_it) has run, by it & 1 (its RS block)
   int* err;              // [1] (ha_persist_kernel) a bounded wait ran out (the search is then not trusted)
-  // (ha_persist_kernel, HA_SPEC) the runner-up: popfirst!'s second-least entry when n_{it+1} is popped, the
+  // (ha_persist_kernel, SPEC) the runner-up: popfirst!'s second-least entry when n_{it+1} is popped, the
   // candidate for n_{it+2}, expanded (and RS_connected) speculatively
   unsigned long long* ngr2;  // [HA_NGR_SLOTS][B][HA_NGR] the runner-up as tagged granules, by it & 3
   int* exs;              // [2][B] speculative expansions finished (neighbour groups, cumulative), by the parity of the runner-up's iteration
@@ -2518,7 +2480,7 @@ __device__ __forceinline__ IterArgs e_par(const IterArgs& A, int B, int np, int 
 
 // pre_wait (ha_persist_kernel): the wait for this iteration's expansion records, run after the open list's loads
 // are issued (the list stands as the previous iteration's bookkeeping left it) so they land meanwhile.
-// SPEC (ha_persist_kernel, HA_SPEC): also the runner-up -- the second-least of popfirst!'s candidates, which is
+// SPEC (ha_persist_kernel, SPEC): also the runner-up -- the second-least of popfirst!'s candidates, which is
 // the next pop unless one of the popped node's children beats it (87 % of the pops of configs[3]) -- published
 // as Q.ngr2 granules after the writes; sr (LDS, kept by the caller across iterations) holds the previous one
 // (10 payload words + valid), and the pop's go word carries skip = hit (the popped node IS the previous
@@ -3068,20 +3030,12 @@ __device__ __forceinline__ BookRec ha_book_pipe(const HaDev& P, const HaSearch& 
 // scenes) is occupancy-bound: 133 VGPRs would allow 3 waves per SIMD; 4 costs 20 B of spills and gains
 // 0.3 ms per plan (r04zc: 29.7 vs 30.0 ms; round 4 had drifted to 169 VGPRs, 2 waves, 31.5 ms).  The
 // tail shape's 12-wave blocks take one CU each either way (6 waves: 80 VGPRs + spills, 0.2 ms slower).
-#ifndef HA_WPE_FULL
-#define HA_WPE_FULL 4
-#endif
-#ifndef HA_WPE_TAIL
-#define HA_WPE_TAIL 1
-#endif
+// (The 6-wave middle shape at 3 waves per SIMD -- 139 VGPRs, no spills, still two blocks per CU -- measured 1.4 ms
+// slower per 256-plan than at 4 with 128 VGPRs and spills, r05zp; kept at 4.)
+constexpr int kWpeTail = 1, kWpeStep = 4;
 constexpr int HA_STAMP_EVERY = 25, HA_STAMP_N = 17;  // [6..11]: bookkeeping phases; [12..16]: block body phases
 template <int HWt, int NBGt, bool RSH = false, bool AST = false>
-// (the 6-wave middle shape at 3 waves per SIMD -- 139 VGPRs, no spills, still two blocks per CU -- measured 1.4 ms
-// slower per 256-plan than at 4 with 128 VGPRs and spills, r05zp; kept at 4)
-#ifndef HA_WPE_MID
-#define HA_WPE_MID 4
-#endif
-__global__ __launch_bounds__(64 * HWt) __attribute__((amdgpu_waves_per_eu(HWt == HW_TAIL ? HA_WPE_TAIL : HWt == 6 ? HA_WPE_MID : HA_WPE_FULL))) void ha_step_kernel(HaDev P, HaSearch Q, IterArgs A, int B, int it) {
+__global__ __launch_bounds__(64 * HWt) __attribute__((amdgpu_waves_per_eu(HWt == HW_TAIL ? kWpeTail : kWpeStep))) void ha_step_kernel(HaDev P, HaSearch Q, IterArgs A, int B, int it) {
   __shared__ int role;
   unsigned long long* stp = nullptr;
   if (HA_STAMP_CODE && A.stamps && it % HA_STAMP_EVERY == 0 && it / HA_STAMP_EVERY < 40 && (int)blockIdx.x < A.stamp_blocks &&
@@ -3166,7 +3120,7 @@ __global__ __launch_bounds__(64 * HWt) __attribute__((amdgpu_waves_per_eu(HWt ==
 // bookkeeping, 2 .. 1 + n_groups the expansion of n_{it+1}.  boot = 1: only the expansion, of n_it itself
 // (node buffer (it - 1) & 1) into E[it & 1], for the first pipelined launch.
 template <int HWt, int NBGt, bool AST = false>
-__global__ __launch_bounds__(64 * HWt) __attribute__((amdgpu_waves_per_eu(HA_WPE_TAIL))) void ha_pipe_kernel(
+__global__ __launch_bounds__(64 * HWt) __attribute__((amdgpu_waves_per_eu(kWpeTail))) void ha_pipe_kernel(
     HaDev P, HaSearch Q, IterArgs A, int B, int it, int boot) {
   __shared__ int role, sh_go;
   unsigned long long* stp = nullptr;
@@ -3257,7 +3211,7 @@ __global__ __launch_bounds__(64 * HWt) __attribute__((amdgpu_waves_per_eu(HA_WPE
 // path in the iteration's parity buffer); the bookkeeping of iteration it waits for E[it & 1] and RS_connected(n_it) and finishes the
 // iteration as ha_step_kernel's finisher.  A finished scene publishes HA_DONE: every block of it leaves its loop.
 // Same operations on the same values as ha_pipe_kernel: the same search, bit for bit.  Every wait is bounded.
-// HA_SPEC (default 1): the speculative runner-up (ha_book_pipe<..., SPEC>).  The bookkeeping of iteration it also
+// SPEC: the speculative runner-up (ha_book_pipe<..., SPEC>).  The bookkeeping of iteration it also
 // publishes r_{it+1}, the second-least of popfirst!'s candidates (Q.ngr2): the next pop is r_{it+1} or one of
 // n_{it+1}'s children (the least of the two), and in configs[3] it is r_{it+1} for 87 % of the pops.  The
 // expansion groups, after n_{it+1}, expand r_{it+1} into E slot 2 + ((it+1) & 3) (Q.exs, by the parity of it+1), the
@@ -3266,13 +3220,10 @@ __global__ __launch_bounds__(64 * HWt) __attribute__((amdgpu_waves_per_eu(HA_WPE
 // skip, the groups and the RS block skip it and the bookkeeping reads the speculative records instead: the lone
 // chain per hit iteration is then the bookkeeping (~14 us) instead of expansion + bookkeeping.  The same records, the same decisions:
 // the search is bit for bit the same (the expansion and RS_connected are functions of the node alone).
-#ifndef HA_SPEC
-#define HA_SPEC 1
-#endif
 // blocks per scene of the persistent launch: two RS_connected blocks, the bookkeeping, ng expansion groups
 #define HA_PERSIST_PER(ng) (3 + (ng))
-template <int HWt, int NBGt, bool SPEC = HA_SPEC, bool AST = false>
-__global__ __launch_bounds__(64 * HWt) __attribute__((amdgpu_waves_per_eu(HWt == HW_TAIL ? HA_WPE_TAIL : 3))) void ha_persist_kernel(
+template <int HWt, int NBGt, bool SPEC = true, bool AST = false>
+__global__ __launch_bounds__(64 * HWt) __attribute__((amdgpu_waves_per_eu(HWt == HW_TAIL ? kWpeTail : 3))) void ha_persist_kernel(
     HaDev P, HaSearch Q, IterArgs A, int B, int it0, double* rs_path2, unsigned char* rs_ok2, int* rs_len2) {
   __shared__ int sh_f;
   __shared__ long long sh_run[12];  // (SPEC, the bookkeeping block) the last runner-up: payload + valid
@@ -3302,10 +3253,7 @@ __global__ __launch_bounds__(64 * HWt) __attribute__((amdgpu_waves_per_eu(HWt ==
     if (p) __hip_atomic_store(p + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   };
   if (item >= 3) {  // the expansion of n_{it+1} (skipped when it is the runner-up), then (SPEC) of r_{it+1}
-#ifndef HA_GROUP_PRIO
-#define HA_GROUP_PRIO 2
-#endif
-    if (HA_GROUP_PRIO) __builtin_amdgcn_s_setprio(HA_GROUP_PRIO);
+    __builtin_amdgcn_s_setprio(2);
     for (int it = it0;; it++) {
       unsigned long long* stp0 = pst(it);  // (stamps: the r job's start / end in slots 6 / 7 of the n job's record)
       for (int job = 0; job < (SPEC ? 2 : 1); job++) {  // (one body for both: a loop, not two inlined copies)
@@ -3375,18 +3323,12 @@ __global__ __launch_bounds__(64 * HWt) __attribute__((amdgpu_waves_per_eu(HWt ==
     }
   }
   // item 1: the bookkeeping of iteration it, it = it0, it0 + 1, ...
-  // on HA_BOOK_WAVES waves of the block (the rest leave: a barrier counts only the waves still running), so its
+  // on 4 waves of the block (the rest leave: a barrier counts only the waves still running), so its
   // block-wide steps (barriers, cross-wave reductions) span fewer waves
-#ifndef HA_BOOK_WAVES
-#define HA_BOOK_WAVES 4
-#endif
-  constexpr int NTB = 64 * (HWt < HA_BOOK_WAVES ? HWt : HA_BOOK_WAVES);
+  constexpr int NTB = 64 * (HWt < 4 ? HWt : 4);
   if ((int)threadIdx.x >= NTB) return;
-#ifndef HA_BOOK_PRIO
-#define HA_BOOK_PRIO 3
-#endif
   // the scene's chain: issued first where its CU is shared (other scenes' blocks, many scenes live)
-  if (HA_BOOK_PRIO) __builtin_amdgcn_s_setprio(HA_BOOK_PRIO);
+  __builtin_amdgcn_s_setprio(3);
   if (SPEC && threadIdx.x < 12) sh_run[threadIdx.x] = 0;  // no runner-up yet: iteration it0's pop is no hit
   __syncthreads();
   int hit = 0;  // (SPEC) n_it is r_{it-1}: its records and RS_connected are the speculative ones
@@ -3583,6 +3525,409 @@ __global__ __launch_bounds__(RT) void ha_retrieve_kernel(const double* start, co
   }
 }
 
+// ---------------------------------------------------------------- mp_ha_plan_astar's host side
+// node, goal and walls of mp_ha_expand / mp_ha_rs_connect on the device, slot = scene.  so: the identity
+// scene list, owned by the caller (the copies are asynchronous: it lives until the caller has synchronised)
+int ha_stage_nodes(mp_ctx* ctx, const mp_ha_params* p, int B, const double* node, const double* goal,
+                   const double* walls, std::vector<int>& so, IterArgs& A) {
+  int st = MP_OK;
+  A.node = mp_upload(ctx, WS_IO0, node, 3 * (size_t)B, &st);
+  A.goal = mp_upload(ctx, WS_IO1, goal, 3 * (size_t)B, &st);
+  A.walls = p->n_walls ? mp_upload(ctx, WS_IO2, walls, 5 * (size_t)p->n_walls * B, &st) : nullptr;
+  so.resize(B);
+  for (int i = 0; i < B; i++) so[i] = i;
+  A.scene_of = mp_upload(ctx, WS_IO3, so.data(), (size_t)B, &st);
+  A.n_active = B;
+  return st;
+}
+
+// The search state (node arrays and open list indexed [scene][node / cell], per-scene records and flags) carved
+// out of one workspace, each array on a 256-byte boundary.  With ws = nullptr only the size is computed: the
+// size and the pointers come from this one list, so an array added here cannot be missing from the size.
+size_t ha_search_layout(HaSearch& Q, char* ws, size_t nB, size_t C, size_t mp) {
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    char* q = ws ? ws + off : nullptr;
+    off += (bytes + 255) & ~(size_t)255;
+    return q;
+  };
+  Q.parent = (long long*)take(nB * C * 8);
+  Q.st = (double*)take(nB * C * 24);
+  Q.index = (long long*)take(nB * C * 8);
+  Q.g = (double*)take(nB * C * 8);
+  Q.h = (double*)take(nB * C * 8);
+  Q.f = (double*)take(nB * C * 8);
+  Q.seq = (long long*)take(nB * C * 8);
+  Q.pos = (int*)take(nB * C * 4);
+  Q.nid = (int*)take(nB * C * 4);
+  Q.of = (double*)take(nB * C * 8);
+  Q.oseq = (long long*)take(nB * C * 8);
+  Q.oid = (int*)take(nB * C * 4);
+  Q.og = (double*)take(nB * C * 8);
+  Q.oix = (long long*)take(nB * C * 8);
+  Q.ost = (double*)take(nB * C * 24);
+  Q.cur_g = (double*)take(nB * 8);
+  Q.cur_ix = (long long*)take(nB * 8);
+  Q.sc_i = (int*)take(nB * SI_N * 4);
+  Q.ctr = (long long*)take(nB * 8);
+  Q.start_index = (long long*)take(nB * 8);
+  Q.pop_seq = (long long*)take(nB * mp * 8);
+  Q.states = (double*)take(nB * mp * 24);
+  Q.node = (double*)take(nB * 48);
+  Q.live = (int*)take(sizeof(int) * (mp + 2));
+  Q.lst = (int*)take(sizeof(int) * 2 * nB);
+  Q.tk = (int*)take(sizeof(int) * 2 * nB);
+  Q.rec = (long long*)take(nB * RC_N * 8);
+  Q.rw = (int*)take(nB * C * 4);
+  Q.orw = (int*)take(nB * C * 4);
+  Q.node_rw = (int*)take(nB * 8);
+  Q.tuv = (double*)take(nB * C * 24);
+  Q.otuv = (double*)take(nB * C * 24);
+  Q.node_tuv = (double*)take(nB * 48);
+  Q.pre = (long long*)take(nB * PRE_W * 8);
+  Q.nx = (int*)take(nB * 4);
+  Q.ngr = (unsigned long long*)take(nB * HA_NGR_SLOTS * HA_NGR * 8);
+  Q.ex = (int*)take(nB * 4);
+  Q.rsr = (int*)take(nB * 8);
+  Q.err = (int*)take(AS_HDR + 3 * sizeof(double));  // the flag, and (mp_ha_plan_astar) the table header behind it
+  Q.ngr2 = (unsigned long long*)take(nB * HA_NGR_SLOTS * HA_NGR * 8);
+  Q.exs = (int*)take(nB * 8);
+  Q.rsrs = (int*)take(nB * 8);
+  Q.nhit = (int*)take(nB * 8);
+  return off;
+}
+
+// the expansion records: 2 parities (E[it & 1]) + 4 runner-up slots (ha_persist_kernel SPEC)
+constexpr size_t HA_NPAR = 6;
+
+// The code object lays the kernel templates' instances out in the order of their first use.  They are named here
+// once in the order mp_ha_plan_astar has always used them in, so that the table below is free to group them by
+// use_astar and the code object still keeps its layout byte for byte (profiles/switch_retire_isa.txt).
+[[maybe_unused]] const void* const kHaKernelOrder[] = {
+    (const void*)ha_persist_kernel<HW_TAIL, NBG_TAIL>,           (const void*)ha_persist_kernel<6, NBG_TAIL>,
+    (const void*)ha_persist_kernel<4, NBG_TAIL>,                 (const void*)ha_persist_kernel<HW_TAIL, NBG_TAIL, true, true>,
+    (const void*)ha_persist_kernel<6, NBG_TAIL, true, true>,     (const void*)ha_persist_kernel<4, NBG_TAIL, true, true>,
+    (const void*)ha_pipe_kernel<HW_TAIL, NBG_TAIL, true>,        (const void*)ha_pipe_kernel<HW_TAIL, NBG_TAIL>,
+    (const void*)ha_step_kernel<HW_TAIL, NBG_TAIL, true, true>,  (const void*)ha_step_kernel<HW_TAIL, NBG_TAIL, true>,
+    (const void*)ha_step_kernel<HW_TAIL, NBG_TAIL, false, true>, (const void*)ha_step_kernel<HW_TAIL, NBG_TAIL>,
+    (const void*)ha_step_kernel<HW_MID, NBG, false, true>,       (const void*)ha_step_kernel<HW_MID, NBG>,
+    (const void*)ha_step_kernel<HW, NBG, false, true>,           (const void*)ha_step_kernel<HW, NBG>};
+
+// The plan's kernels, one row per value of use_astar (the AST instances look astar_heuristic's table up).
+using HaStepFn = void (*)(HaDev, HaSearch, IterArgs, int, int);
+using HaPipeFn = void (*)(HaDev, HaSearch, IterArgs, int, int, int);
+struct HaKernels {
+  HaStepFn full, mid, tail, tail_rsh;  // ha_step_kernel: 4-, 6- and 12-wave blocks, the last with the word units
+  HaPipeFn pipe;
+  const void* persist[3];              // ha_persist_kernel on 12-, 6- and 4-wave blocks
+};
+constexpr int kPersistHW[3] = {HW_TAIL, 6, 4};
+const HaKernels kHaKernels[2] = {
+    {ha_step_kernel<HW, NBG>, ha_step_kernel<HW_MID, NBG>, ha_step_kernel<HW_TAIL, NBG_TAIL>,
+     ha_step_kernel<HW_TAIL, NBG_TAIL, true>, ha_pipe_kernel<HW_TAIL, NBG_TAIL>,
+     {reinterpret_cast<const void*>(ha_persist_kernel<HW_TAIL, NBG_TAIL>),
+      reinterpret_cast<const void*>(ha_persist_kernel<6, NBG_TAIL>),
+      reinterpret_cast<const void*>(ha_persist_kernel<4, NBG_TAIL>)}},
+    {ha_step_kernel<HW, NBG, false, true>, ha_step_kernel<HW_MID, NBG, false, true>,
+     ha_step_kernel<HW_TAIL, NBG_TAIL, false, true>, ha_step_kernel<HW_TAIL, NBG_TAIL, true, true>,
+     ha_pipe_kernel<HW_TAIL, NBG_TAIL, true>,
+     {reinterpret_cast<const void*>(ha_persist_kernel<HW_TAIL, NBG_TAIL, true, true>),
+      reinterpret_cast<const void*>(ha_persist_kernel<6, NBG_TAIL, true, true>),
+      reinterpret_cast<const void*>(ha_persist_kernel<4, NBG_TAIL, true, true>)}}};
+
+// the live-count polls' events, released on every return path
+constexpr int HA_NCK = 4;
+struct HaEvents {
+  hipEvent_t e[HA_NCK] = {};
+  ~HaEvents() {
+    for (hipEvent_t x : e)
+      if (x) (void)hipEventDestroy(x);
+  }
+};
+
+// The per-plan tables, one launch each ahead of the search: pose and heading terms of every lattice heading,
+// the walls' SAT tables.
+int ha_plan_tables(mp_ctx* ctx, const mp_ha_params* p, const HaDev& D, int B, IterArgs& A) {
+  const int np = p->n_prim;
+  // the pose table (A.ptab): the neighbour sweeps' heading terms for every lattice heading -- regulated
+  // headings are round(modπ(ψ)/res)·res, so m spans round(±π/res) (one spare step each side); the few
+  // microseconds of one launch per plan.
+  {
+    const double r = p->res[2];
+    const int nsw = p->n_col > 5 ? (p->n_col - 1) / 5 + 1 : 1;
+    const double lo = std::floor(-MPJ_PI / r) - 1, hi = std::ceil(MPJ_PI / r) + 1;
+    const bool ok = r > 0 && hi - lo < 4096;
+    const int mlo = ok ? (int)lo : 0, nm = ok ? (int)(hi - lo) + 1 : 0;
+    const size_t n = (size_t)nm * np * nsw;
+    double* tab = ok ? (double*)mp_ws(ctx, WS_IO10, sizeof(double) * 4 * n) : nullptr;
+    if (ok && !tab) return MP_ERR_NOMEM;
+    if (tab) {
+      hipLaunchKernelGGL(ha_pose_table_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, D,
+                         (const double*)ctx->ha_paths_candi, mlo, nm, nsw, tab);
+      MP_HIP(ctx, hipGetLastError());
+    }
+    A.ptab = tab;
+    A.pt_mlo = mlo;
+    A.pt_nm = nm;
+    A.pt_nsw = nsw;
+    double* htn = ok ? (double*)mp_ws(ctx, WS_IO13, sizeof(double) * (2 * (size_t)nm + 4 * (size_t)nm * np)) : nullptr;
+    if (ok && !htn) return MP_ERR_NOMEM;
+    if (htn) {
+      hipLaunchKernelGGL(ha_head_table_kernel, dim3((unsigned)((nm * np + 255) / 256)), dim3(256), 0, ctx->stream, D,
+                         (const double*)ctx->ha_states_candi, mlo, nm, htn, htn + 2 * (size_t)nm);
+      MP_HIP(ctx, hipGetLastError());
+    }
+    A.htn = htn;
+    A.htk = htn ? htn + 2 * (size_t)nm : nullptr;
+  }
+  if (p->n_walls) {
+    double* wt = (double*)mp_ws(ctx, WS_IO8, sizeof(double) * (size_t)B * p->n_walls * WT);
+    if (!wt) return MP_ERR_NOMEM;
+    hipLaunchKernelGGL(ha_wall_kernel, dim3((unsigned)((B * p->n_walls + 63) / 64)), dim3(64), 0, ctx->stream, D, B,
+                       A.walls, wt);
+    A.wtab = wt;
+  }
+  return MP_OK;
+}
+
+// The whole search loop, enqueued without host round trips: iteration i = one ha_step_kernel
+// (RS_connected + 62 neighbours of every live scene, the bookkeeping + the next pop by the scene's
+// last neighbour-group block, beside RS_connected; the finisher publishes or undoes).  live[i] (scenes
+// still searching after iteration i) is copied back once per chunk of CH iterations; the host stays
+// at most two chunks ahead of the device and stops enqueueing when a copied count is 0 (at most
+// every scene's max_pops iterations).  (Round 1 fused the bookkeeping behind an agent-scope release
+// in every block -- an L2 write-back each -- and measured 67-90 ms vs 40 ms; ha_step_kernel hands
+// its records over with agent-coherent stores instead, so no block writes back its L2.)
+// *persisted: the search ended in the persistent launch; *waited: a launch with bounded cross-block waits ran
+// (they report through Q.err).
+int ha_search_loop(mp_ctx* ctx, const HaDev& D, const HaSearch& Q, IterArgs& A, int B, bool use_astar,
+                   const HaEvents& ev, bool* persisted, bool* waited) {
+  const int np = D.n_prim, mp = Q.mp;
+  const size_t nB = (size_t)B;
+  const HaKernels& K = kHaKernels[use_astar ? 1 : 0];
+  constexpr int CH = 16;  // iterations per live-count poll
+  int* hl = (int*)mp_pinned(ctx, sizeof(int) * HA_NCK);
+  if (!hl) return mp_fail(ctx, MP_ERR_NOMEM, "pinned allocation failed");
+  const int per = 1 + (np + NBG - 1) / NBG, per_tail = 1 + (np + NBG_TAIL - 1) / NBG_TAIL;
+  const int per_pipe = 2 + (np + NBG_TAIL - 1) / NBG_TAIL;
+  // the tail's rs_heuristic word units (ha_iter_body RSH): group g·4 + c holds neighbours 16g.. and word chunk
+  // c, so there must be a group for every (16-neighbour set, chunk) -- n_prim mod 16 in {0, 13, 14, 15} with
+  // 4 neighbours per group (62: yes); otherwise the groups' own word search.
+  const bool tail_rsh = per_tail - 1 >= 4 * ((np + 15) / 16);
+  const bool tail_pipe = tail_rsh;
+  // the persistent tail (ha_persist_kernel): one cooperative launch for the rest of the search once every block
+  // of it fits the device at once.  Without cooperative launches (or when one is refused) the tail runs one
+  // ha_pipe_kernel launch per iteration; MPGPU_HA_PERSIST=0 selects that fallback (a test hook: the same
+  // results, tests/test_gpu_hastar.py runs it)
+  const bool persist_env = !getenv("MPGPU_HA_PERSIST") || atoi(getenv("MPGPU_HA_PERSIST")) != 0;
+  int persist_cap = 0;
+  // the persistent kernel's block: 12 waves (one per CU: 14 scenes per launch), 6 (two per CU: 28 scenes; the
+  // groups' sweep on 3 waves beside the 3 word waves) or 4 (three per CU: 42 scenes; the sweep on one wave).
+  // Per call, the largest block that holds the whole batch in one launch from the start, and 6 when none does
+  // (the tail then starts at 28 live scenes).  Measured: a lone scenario 18.7 / 18.9 / 20.4 us per iteration
+  // with 12 / 6 / 4 (r05zg, r05zh); the 256-plan 24.0 ms with 6 or 4, 24.7 with 12; a 32-scene shard 16.4 ms with
+  // 4 against 18.4-20.1 with 6, whose tail starts only at 28 live scenes, two blocks sharing each CU.
+  const int per_ps = HA_PERSIST_PER((np + NBG_TAIL - 1) / NBG_TAIL);
+  int* pcap = use_astar ? ctx->ha_pcap_ast : ctx->ha_pcap;  // co-resident blocks of each on this context's device (0: no cooperative launch)
+  int phw = kPersistHW[1];
+  const void* persist_fn = K.persist[1];
+  double* rs_path2 = nullptr;
+  int* rs_i2 = nullptr;
+  if (tail_pipe && persist_env) {
+    if (pcap[0] < 0) {
+      int cus = 0, coop = 0;
+      const bool ok = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) == hipSuccess &&
+                      hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, ctx->device) == hipSuccess && coop;
+      for (int v = 0; v < 3; v++) {
+        int nbpc = 0;
+        pcap[v] = ok && hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbpc, K.persist[v], 64 * kPersistHW[v], 0) == hipSuccess
+                      ? nbpc * cus : 0;
+      }
+      (void)hipGetLastError();
+    }
+    int v = 1;
+    for (int c = 0; c < 3; c++)
+      if (B * per_ps <= pcap[c]) { v = c; break; }
+    phw = kPersistHW[v];
+    persist_fn = K.persist[v];
+    persist_cap = pcap[v];
+    // RS_connected's outputs by slot (ha_persist_kernel rs_slot): HA_NPAR slots of rs_path, rs_ok (bytes), rs_len
+    rs_path2 = (double*)mp_ws(ctx, WS_IO15, sizeof(double) * HA_NPAR * nB * MAXPATH * 3);
+    rs_i2 = (int*)mp_ws(ctx, WS_IO16, sizeof(int) * 2 * HA_NPAR * nB);
+    if (!rs_path2 || !rs_i2) return MP_ERR_NOMEM;
+  }
+  // the pipelined launch's expansion blocks wait for their bookkeeping on a CU each: it pays only while the
+  // whole launch is resident at once (one 12-wave block per CU).  (Measured and removed: the full-width shape
+  // pipelined the same way, 0.4-0.9 ms slower per 256-plan, r05u/r05v: its bookkeeping publishes the pop ~10 us
+  // after its start, so pop + expansion is no shorter than expansion + the whole bookkeeping.)
+  constexpr int pipe_blocks = 256;
+  int piped = 0;  // the format of the records the last launch left in E[it & 1]: 0 none, 2 tail
+  // iteration it >= 2 works on the compact list of scenes still live (written by the previous
+  // bookkeeping launch, count on the device); the host sizes the grids by the last live count it has
+  // seen (an upper bound: it only decreases) and switches to the tail shape once that many scenes
+  // fit in about two blocks per CU
+  // the middle shape: HW_MID-wave blocks, 16 neighbours each (5 blocks per scene), once known * 5 fits in
+  // mid_blocks blocks.  r05x: the 6-wave middle shape for 16..102 live scenes and the tail from 15 (its
+  // pipelined / persistent forms from 14) -- 256-plan 25.6 -> 24.9 ms, the largest strided / contiguous shard
+  // 21.0 -> 19.2 / 17.9 -> 17.6 ms (the 12-wave tail step from 30 live scenes, round 4's threshold, and no middle)
+  constexpr int tail_blocks = 256;
+  constexpr int mid_blocks = 512;
+  int known = B;
+  int chunk = 0, checked = 0;
+  bool finished = false;
+  *persisted = *waited = false;
+  for (int it = 1; it <= mp && !finished; it++) {
+    A.scene_of = it == 1 ? nullptr : Q.lst + ((it - 1) & 1) * B;
+    A.n_live = it == 1 ? nullptr : Q.live + (it - 1);
+    A.n_active = known;
+    A.node = Q.node + (size_t)((it - 1) & 1) * 3 * B;  // the previous iteration's pops
+    A.node_rw = Q.node_rw + (size_t)((it - 1) & 1) * B;
+    A.node_tuv = Q.node_tuv + (size_t)((it - 1) & 1) * 3 * B;
+    const auto step = [&](HaStepFn fn, int blocks, int threads) {
+      piped = 0;
+      hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(threads), 0, ctx->stream, D, Q, A, B, it);
+    };
+    // the current nodes' expansion, ahead of the first pipelined or persistent launch (boot = 1)
+    const auto bootstrap = [&] {
+      if (piped == 2) return;
+      hipLaunchKernelGGL(K.pipe, dim3((unsigned)(known * per_pipe)), dim3(64 * HW_TAIL), 0, ctx->stream, D, Q, A, B,
+                         it, 1);
+      piped = 2;
+      *waited = true;
+    };
+    const bool tail = known * per_tail <= tail_blocks;
+    if (tail_pipe && known * per_ps <= persist_cap) {
+      // the rest of the search in one cooperative launch, after the current nodes' expansion
+      bootstrap();
+      unsigned char* rs_ok2 = reinterpret_cast<unsigned char*>(rs_i2);
+      int* rs_len2 = rs_i2 + HA_NPAR * nB;
+      int it0 = it;
+      void* args[] = {(void*)&D, (void*)&Q, &A, &B, &it0, &rs_path2, &rs_ok2, &rs_len2};
+      // (MPGPU_HA_COOP=0: an ordinary launch of the same grid, co-resident by the occupancy check alone -- for
+      // rocprofv3 runs: the profiler's exit handlers crash in a process that made a cooperative launch)
+      static const bool coop_env = !getenv("MPGPU_HA_COOP") || atoi(getenv("MPGPU_HA_COOP")) != 0;
+      const hipError_t le =
+          coop_env ? hipLaunchCooperativeKernel(persist_fn, dim3((unsigned)(known * per_ps)), dim3(64 * phw), args, 0,
+                                                ctx->stream)
+                   : hipLaunchKernel(persist_fn, dim3((unsigned)(known * per_ps)), dim3(64 * phw), args, 0, ctx->stream);
+      if (le != hipSuccess) {
+        // refused (e.g. the device's co-residency changed under this context): the per-iteration pipelined
+        // tail from this iteration on -- the bootstrap above already expanded the current nodes
+        (void)hipGetLastError();
+        persist_cap = 0;
+        pcap[0] = pcap[1] = pcap[2] = 0;
+        it--;
+        continue;
+      }
+      *persisted = true;
+      break;
+    } else if (tail && tail_pipe && known * per_pipe <= pipe_blocks) {
+      bootstrap();
+      hipLaunchKernelGGL(K.pipe, dim3((unsigned)(known * per_pipe)), dim3(64 * HW_TAIL), 0, ctx->stream, D, Q, A, B,
+                         it, 0);
+    } else if (tail) {  // with the word units: + the prescan block per scene
+      step(tail_rsh ? K.tail_rsh : K.tail, known * (per_tail + (tail_rsh ? 1 : 0)), 64 * HW_TAIL);
+    } else if (known * per <= mid_blocks) {
+      step(K.mid, known * per, 64 * HW_MID);
+    } else {
+      step(K.full, known * per, HT);
+    }
+    if (hipGetLastError() != hipSuccess) return mp_fail(ctx, MP_ERR_HIP, "ha kernel launch failed");
+    // (Measured and removed: polling the live count every 4 iterations near the persistent tail's threshold,
+    // 1 ms slower per 256-plan, r05zn.)
+    if (it % CH == 0 || it == mp) {
+      const int slot = chunk % HA_NCK;
+      if (hipMemcpyAsync(hl + slot, Q.live + it, sizeof(int), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+          hipEventRecord(ev.e[slot], ctx->stream) != hipSuccess)
+        return mp_fail(ctx, MP_ERR_HIP, "live-count copy failed");
+      chunk++;
+      // poll finished chunks without blocking; block only when two chunks ahead
+      while (checked < chunk) {
+        const int cs = checked % HA_NCK;
+        const bool must = chunk - checked > 2;
+        const hipError_t q = must ? hipEventSynchronize(ev.e[cs]) : hipEventQuery(ev.e[cs]);
+        if (q == hipErrorNotReady) break;
+        if (q != hipSuccess) return mp_fail(ctx, MP_ERR_HIP, "event wait failed");
+        if (hl[cs] == 0) { finished = true; break; }
+        known = std::min(known, std::max(hl[cs], 1));
+        checked++;
+      }
+    }
+  }
+  return MP_OK;
+}
+
+// The read-back once the loop is enqueued: the diagnostics, the bounded waits' verdict, the per-scene counters,
+// then the used prefix of pop_seq / states / RS paths.
+int ha_read_back(mp_ctx* ctx, const HaSearch& Q, const IterArgs& A, int B, int stamp_slots, bool persisted,
+                 bool waited, int32_t* found, int32_t* pops, int32_t* n_nodes, int64_t* pop_seq, int32_t* n_states,
+                 double* states_out, int32_t* rs_len, double* rs_path) {
+  const size_t nB = (size_t)B;
+  const int mp = Q.mp;
+  int st = MP_OK;
+  if (A.stamps) {  // diagnostics: raw stamps to $MPGPU_HA_STAMPS_OUT (tools/ha_stamps.py reads them)
+    std::vector<unsigned long long> h((size_t)HA_STAMP_N * stamp_slots * A.stamp_blocks);
+    MP_HIP(ctx, hipMemcpyAsync(h.data(), A.stamps, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    MP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const char* fn = getenv("MPGPU_HA_STAMPS_OUT");
+    if (FILE* f = fopen(fn ? fn : "ha_stamps.bin", "wb")) {
+      const long long hdr[5] = {B, stamp_slots, A.stamp_blocks, HA_STAMP_EVERY, HA_STAMP_N};
+      fwrite(hdr, sizeof hdr, 1, f);
+      fwrite(h.data(), 8, h.size(), f);
+      fclose(f);
+    }
+  }
+  if (persisted || waited) {  // a bounded wait (persistent or pipelined launch) that ran out: not trusted
+    int err = 0;
+    if (hipMemcpyAsync(&err, Q.err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+        hipStreamSynchronize(ctx->stream) != hipSuccess)
+      return mp_fail(ctx, MP_ERR_HIP, "persistent search failed");
+    if (err) return mp_fail(ctx, MP_ERR_HIP, "Hybrid A* search: a cross-block wait timed out");
+  }
+  if (getenv("MPGPU_HA_SPEC_STATS")) {  // diagnostics: how often the speculative runner-up was the next pop
+    std::vector<int> nh(2 * nB);
+    MP_HIP(ctx, hipMemcpyAsync(nh.data(), Q.nhit, sizeof(int) * 2 * nB, hipMemcpyDeviceToHost, ctx->stream));
+    MP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    long long hits = 0, pubs = 0;
+    for (size_t i = 0; i < nB; i++) { hits += nh[i]; pubs += nh[nB + i]; }
+    fprintf(stderr, "[ha spec] persisted %d: runner-ups published %lld, pops that were the runner-up %lld\n",
+            (int)persisted, pubs, hits);
+  }
+  // outputs: per-scene counters, then the used prefix of pop_seq / states / RS paths
+  std::vector<int> si(SI_N * nB);
+  if ((st = mp_download(ctx, si.data(), (const int*)Q.sc_i, SI_N * nB))) return st;
+  if (hipStreamSynchronize(ctx->stream) != hipSuccess) return mp_fail(ctx, MP_ERR_HIP, "search failed");
+  int max_loop = 0, max_ns = 0, max_rs = 0;
+  for (int b = 0; b < B; b++) {
+    found[b] = si[SI_FOUND * B + b];
+    pops[b] = si[SI_LOOP * B + b];
+    n_nodes[b] = si[SI_NNODES * B + b];
+    n_states[b] = si[SI_NSTATES * B + b];
+    rs_len[b] = found[b] ? si[SI_RSLEN * B + b] : 0;
+    max_loop = std::max(max_loop, pops[b]);
+    max_ns = std::max(max_ns, n_states[b]);
+    max_rs = std::max(max_rs, rs_len[b]);
+  }
+  if (max_loop > 0)
+    MP_HIP(ctx, hipMemcpy2DAsync(pop_seq, sizeof(int64_t) * mp, Q.pop_seq, sizeof(long long) * mp,
+                                 sizeof(long long) * max_loop, nB, hipMemcpyDeviceToHost, ctx->stream));
+  if (max_ns > 0)
+    MP_HIP(ctx, hipMemcpy2DAsync(states_out, sizeof(double) * 3 * mp, Q.states, sizeof(double) * 3 * mp,
+                                 sizeof(double) * 3 * max_ns, nB, hipMemcpyDeviceToHost, ctx->stream));
+  std::vector<double> rsb;
+  if (max_rs > 0) {
+    rsb.resize(nB * max_rs * 3);
+    MP_HIP(ctx, hipMemcpy2DAsync(rsb.data(), sizeof(double) * 3 * max_rs, A.rs_path, sizeof(double) * 3 * MAXPATH,
+                                 sizeof(double) * 3 * max_rs, nB, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  MP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (int b = 0; b < B; b++)
+    if (found[b])
+      std::copy(rsb.begin() + (size_t)b * max_rs * 3, rsb.begin() + ((size_t)b * max_rs + rs_len[b]) * 3,
+                rs_path + (size_t)b * MAXPATH * 3);
+  return MP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3678,12 +4023,8 @@ int mp_ha_expand(mp_ctx* ctx, const mp_ha_params* p, int32_t B, const double* no
   MP_HIP(ctx, hipSetDevice(ctx->device));
   const size_t np = p->n_prim;
   IterArgs A{};
-  A.node = mp_upload(ctx, WS_IO0, node, 3 * (size_t)B, &st);
-  A.goal = mp_upload(ctx, WS_IO1, goal, 3 * (size_t)B, &st);
-  A.walls = p->n_walls ? mp_upload(ctx, WS_IO2, walls, 5 * (size_t)p->n_walls * B, &st) : nullptr;
-  std::vector<int> so(B);
-  for (int i = 0; i < B; i++) so[i] = i;
-  A.scene_of = mp_upload(ctx, WS_IO3, so.data(), (size_t)B, &st);
+  std::vector<int> so;
+  st = ha_stage_nodes(ctx, p, B, node, goal, walls, so, A);
   A.nb = mp_alloc_out(ctx, WS_IO4, nb_states, 3 * np * B, &st);
   A.idx = (long long*)mp_alloc_out(ctx, WS_IO5, idx, np * B, &st);
   A.fr = mp_alloc_out(ctx, WS_IO6, free_, np * B, &st);
@@ -3691,7 +4032,6 @@ int mp_ha_expand(mp_ctx* ctx, const mp_ha_params* p, int32_t B, const double* no
   if (st) return st;
   A.sc = ctx->ha_states_candi;
   A.pc = ctx->ha_paths_candi;
-  A.n_active = B;
   A.do_rs = 0;
   A.do_exp = 1;
   if ((st = launch_iter(ctx, D, A))) return st;
@@ -3713,17 +4053,12 @@ int mp_ha_rs_connect(mp_ctx* ctx, const mp_ha_params* p, int32_t B, const double
   ha_cull_ok(ctx, p, &D, B, walls, node, goal);
   MP_HIP(ctx, hipSetDevice(ctx->device));
   IterArgs A{};
-  A.node = mp_upload(ctx, WS_IO0, node, 3 * (size_t)B, &st);
-  A.goal = mp_upload(ctx, WS_IO1, goal, 3 * (size_t)B, &st);
-  A.walls = p->n_walls ? mp_upload(ctx, WS_IO2, walls, 5 * (size_t)p->n_walls * B, &st) : nullptr;
-  std::vector<int> so(B);
-  for (int i = 0; i < B; i++) so[i] = i;
-  A.scene_of = mp_upload(ctx, WS_IO3, so.data(), (size_t)B, &st);
+  std::vector<int> so;
+  st = ha_stage_nodes(ctx, p, B, node, goal, walls, so, A);
   A.rs_ok = mp_alloc_out(ctx, WS_IO4, ok, (size_t)B, &st);
   A.rs_path = mp_alloc_out(ctx, WS_IO5, path, (size_t)B * MAXPATH * 3, &st);
   A.rs_len = mp_alloc_out(ctx, WS_IO6, path_len, (size_t)B, &st);
   if (st) return st;
-  A.n_active = B;
   A.do_rs = 1;
   A.do_exp = 0;
   if ((st = launch_iter(ctx, D, A))) return st;
@@ -3849,60 +4184,13 @@ int mp_ha_plan_astar(mp_ctx* ctx, const mp_ha_params* p, int32_t B, const double
                           (long long)(mpj_round((p->stbound[5] - p->stbound[4]) / p->res[2]) + 1);
   MP_CHECK(ctx, ncell > 0 && ncell < (1LL << 26), "state lattice too large (%lld cells)", ncell);
   const size_t C = (size_t)ncell + 1, nB = (size_t)B;
-  // search state: node arrays and open list indexed [scene][node / cell]
-  const size_t per_cell = 8 + 24 + 8 + 24 + 8 + 4 + 4 + 8 + 8 + 4 + 8 + 8 + 24 + 4 + 4 + 24 + 24;
-  char* ws = (char*)mp_ws(ctx, WS_HA2, nB * C * per_cell + nB * (SI_N * 4 + 32) + nB * mp * 32 + nB * 48 +
-                                           sizeof(int) * (mp + 2) + sizeof(int) * 4 * nB + nB * RC_N * 8 + nB * 8 + nB * 48 + nB * PRE_W * 8 + nB * 16 + 4 + nB * HA_NGR_SLOTS * HA_NGR * 8 + 256 * 57 +
-                                           nB * HA_NGR_SLOTS * HA_NGR * 8 + nB * 24 + 256 * 4);
-  if (!ws) return MP_ERR_NOMEM;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* q = ws + off; off += (bytes + 255) & ~(size_t)255; return q; };
   HaSearch Q;
   Q.C = (int)C;
   Q.mp = mp;
-  Q.parent = (long long*)take(nB * C * 8);
-  Q.st = (double*)take(nB * C * 24);
-  Q.index = (long long*)take(nB * C * 8);
-  Q.g = (double*)take(nB * C * 8);
-  Q.h = (double*)take(nB * C * 8);
-  Q.f = (double*)take(nB * C * 8);
-  Q.seq = (long long*)take(nB * C * 8);
-  Q.pos = (int*)take(nB * C * 4);
-  Q.nid = (int*)take(nB * C * 4);
-  Q.of = (double*)take(nB * C * 8);
-  Q.oseq = (long long*)take(nB * C * 8);
-  Q.oid = (int*)take(nB * C * 4);
-  Q.og = (double*)take(nB * C * 8);
-  Q.oix = (long long*)take(nB * C * 8);
-  Q.ost = (double*)take(nB * C * 24);
-  Q.cur_g = (double*)take(nB * 8);
-  Q.cur_ix = (long long*)take(nB * 8);
-  Q.sc_i = (int*)take(nB * SI_N * 4);
-  Q.ctr = (long long*)take(nB * 8);
-  Q.start_index = (long long*)take(nB * 8);
-  Q.pop_seq = (long long*)take(nB * mp * 8);
-  Q.states = (double*)take(nB * mp * 24);
-  Q.node = (double*)take(nB * 48);
-  Q.live = (int*)take(sizeof(int) * (mp + 2));
-  Q.lst = (int*)take(sizeof(int) * 2 * nB);
-  Q.tk = (int*)take(sizeof(int) * 2 * nB);
-  Q.rec = (long long*)take(nB * RC_N * 8);
-  Q.rw = (int*)take(nB * C * 4);
-  Q.orw = (int*)take(nB * C * 4);
-  Q.node_rw = (int*)take(nB * 8);
-  Q.tuv = (double*)take(nB * C * 24);
-  Q.otuv = (double*)take(nB * C * 24);
-  Q.node_tuv = (double*)take(nB * 48);
-  Q.pre = (long long*)take(nB * PRE_W * 8);
-  Q.nx = (int*)take(nB * 4);
-  Q.ngr = (unsigned long long*)take(nB * HA_NGR_SLOTS * HA_NGR * 8);
-  Q.ex = (int*)take(nB * 4);
-  Q.rsr = (int*)take(nB * 8);
-  Q.err = (int*)take(AS_HDR + 3 * sizeof(double));  // the flag, and (mp_ha_plan_astar) the table header behind it
-  Q.ngr2 = (unsigned long long*)take(nB * HA_NGR_SLOTS * HA_NGR * 8);
-  Q.exs = (int*)take(nB * 8);
-  Q.rsrs = (int*)take(nB * 8);
-  Q.nhit = (int*)take(nB * 8);
+  const size_t ws_bytes = ha_search_layout(Q, nullptr, nB, C, (size_t)mp);
+  char* ws = (char*)mp_ws(ctx, WS_HA2, ws_bytes);
+  if (!ws) return MP_ERR_NOMEM;
+  MP_CHECK(ctx, ha_search_layout(Q, ws, nB, C, (size_t)mp) == ws_bytes, "search workspace: the two layout passes differ");
   IterArgs A{};
   A.goal = mp_upload(ctx, WS_HA0, goal, 3 * nB, &st);
   A.walls = p->n_walls ? mp_upload(ctx, WS_HA1, walls, 5 * (size_t)p->n_walls * B, &st) : nullptr;
@@ -3919,58 +4207,19 @@ int mp_ha_plan_astar(mp_ctx* ctx, const mp_ha_params* p, int32_t B, const double
     MP_HIP(ctx, hipMemcpyAsync(reinterpret_cast<char*>(Q.err) + AS_HDR, hd, 3 * sizeof(double), hipMemcpyHostToDevice,
                                ctx->stream));
   }
-  // the expansion records: 2 parities (E[it & 1]) + (HA_SPEC) 4 runner-up slots
-  constexpr size_t NPAR = HA_SPEC ? 6 : 2;
-  A.h = (double*)mp_ws(ctx, WS_IO1, sizeof(double) * nB * np * NPAR);
   // the expansion records (nb, idx, fr, h, hw, hp_*) hold two parities: ha_pipe_kernel's launch it reads E[it & 1]
   // while its expansion blocks write E[(it + 1) & 1]; every other launch uses parity 0
-  A.nb = (double*)mp_ws(ctx, WS_IO2, sizeof(double) * nB * np * 3 * NPAR);
-  A.idx = (long long*)mp_ws(ctx, WS_IO3, sizeof(long long) * nB * np * NPAR);
-  A.fr = (unsigned char*)mp_ws(ctx, WS_IO4, nB * np * NPAR);
+  A.h = (double*)mp_ws(ctx, WS_IO1, sizeof(double) * nB * np * HA_NPAR);
+  A.nb = (double*)mp_ws(ctx, WS_IO2, sizeof(double) * nB * np * 3 * HA_NPAR);
+  A.idx = (long long*)mp_ws(ctx, WS_IO3, sizeof(long long) * nB * np * HA_NPAR);
+  A.fr = (unsigned char*)mp_ws(ctx, WS_IO4, nB * np * HA_NPAR);
   A.rs_ok = (unsigned char*)mp_ws(ctx, WS_IO5, nB);
   A.rs_len = (int*)mp_ws(ctx, WS_IO6, sizeof(int) * nB);
   A.rs_path = (double*)mp_ws(ctx, WS_IO7, sizeof(double) * nB * MAXPATH * 3);
-  A.hw = (int*)mp_ws(ctx, WS_IO9, sizeof(int) * nB * np * NPAR);
+  A.hw = (int*)mp_ws(ctx, WS_IO9, sizeof(int) * nB * np * HA_NPAR);
   if (st || !A.h || !A.nb || !A.idx || !A.fr || !A.rs_ok || !A.rs_len || !A.rs_path || !A.hw)
     return st ? st : MP_ERR_NOMEM;
-  // the pose table (A.ptab): the neighbour sweeps' heading terms for every lattice heading -- regulated
-  // headings are round(modπ(ψ)/res)·res, so m spans round(±π/res) (one spare step each side); the few
-  // microseconds of one launch per plan.
-  {
-    const double r = p->res[2];
-    const int nsw = p->n_col > 5 ? (p->n_col - 1) / 5 + 1 : 1;
-    const double lo = std::floor(-MPJ_PI / r) - 1, hi = std::ceil(MPJ_PI / r) + 1;
-    const bool ok = r > 0 && hi - lo < 4096;
-    const int mlo = ok ? (int)lo : 0, nm = ok ? (int)(hi - lo) + 1 : 0;
-    const size_t n = (size_t)nm * np * nsw;
-    double* tab = ok ? (double*)mp_ws(ctx, WS_IO10, sizeof(double) * 4 * n) : nullptr;
-    if (ok && !tab) return MP_ERR_NOMEM;
-    if (tab) {
-      hipLaunchKernelGGL(ha_pose_table_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, D,
-                         (const double*)ctx->ha_paths_candi, mlo, nm, nsw, tab);
-      MP_HIP(ctx, hipGetLastError());
-    }
-    A.ptab = tab;
-    A.pt_mlo = mlo;
-    A.pt_nm = nm;
-    A.pt_nsw = nsw;
-    double* htn = ok ? (double*)mp_ws(ctx, WS_IO13, sizeof(double) * (2 * (size_t)nm + 4 * (size_t)nm * np)) : nullptr;
-    if (ok && !htn) return MP_ERR_NOMEM;
-    if (htn) {
-      hipLaunchKernelGGL(ha_head_table_kernel, dim3((unsigned)((nm * np + 255) / 256)), dim3(256), 0, ctx->stream, D,
-                         (const double*)ctx->ha_states_candi, mlo, nm, htn, htn + 2 * (size_t)nm);
-      MP_HIP(ctx, hipGetLastError());
-    }
-    A.htn = htn;
-    A.htk = htn ? htn + 2 * (size_t)nm : nullptr;
-  }
-  if (p->n_walls) {
-    double* wt = (double*)mp_ws(ctx, WS_IO8, sizeof(double) * nB * p->n_walls * WT);
-    if (!wt) return MP_ERR_NOMEM;
-    hipLaunchKernelGGL(ha_wall_kernel, dim3((unsigned)((B * p->n_walls + 63) / 64)), dim3(64), 0, ctx->stream, D, B,
-                       A.walls, wt);
-    A.wtab = wt;
-  }
+  if ((st = ha_plan_tables(ctx, p, D, B, A))) return st;
   A.coherent = 1;
   A.dnid = Q.nid;  // the Dict pre-check: groups skip rs_heuristic when no neighbour of theirs can use it
   A.dg = Q.g;
@@ -3998,102 +4247,10 @@ int mp_ha_plan_astar(mp_ctx* ctx, const mp_ha_params* p, int32_t B, const double
   MP_CHECK(ctx, A.do_rs && A.do_exp, "ha_step_kernel needs both block roles");
   A.rs_path_free_only = 1;
   A.n_active = B;
-  MP_HIP(ctx, hipMemsetAsync(Q.pop_seq, 0xff, nB * mp * 8, ctx->stream));  // -1 past each scene's pops
-  MP_HIP(ctx, hipMemsetAsync(Q.live, 0, sizeof(int) * (mp + 2), ctx->stream));
-  MP_HIP(ctx, hipMemsetAsync(Q.tk, 0, sizeof(int) * 2 * nB, ctx->stream));  // the finishers reset them
-  MP_HIP(ctx, hipMemsetAsync(Q.rec, 0, sizeof(long long) * RC_N * nB, ctx->stream));  // record-ready flags
-  MP_HIP(ctx, hipMemsetAsync(Q.nx, 0, sizeof(int) * nB, ctx->stream));  // ha_pipe_kernel's pop flags
-  MP_HIP(ctx, hipMemsetAsync(Q.ngr, 0, sizeof(unsigned long long) * nB * HA_NGR_SLOTS * HA_NGR, ctx->stream));  // granule tags
-  MP_HIP(ctx, hipMemsetAsync(Q.ex, 0, sizeof(int) * nB, ctx->stream));  // ha_persist_kernel's flags
-  MP_HIP(ctx, hipMemsetAsync(Q.rsr, 0, sizeof(int) * 2 * nB, ctx->stream));
-  MP_HIP(ctx, hipMemsetAsync(Q.ngr2, 0, sizeof(unsigned long long) * nB * HA_NGR_SLOTS * HA_NGR, ctx->stream));  // (HA_SPEC)
-  MP_HIP(ctx, hipMemsetAsync(Q.exs, 0, sizeof(int) * 2 * nB, ctx->stream));
-  MP_HIP(ctx, hipMemsetAsync(Q.rsrs, 0, sizeof(int) * 2 * nB, ctx->stream));
-  MP_HIP(ctx, hipMemsetAsync(Q.nhit, 0, sizeof(int) * 2 * nB, ctx->stream));
-  MP_HIP(ctx, hipMemsetAsync(Q.err, 0, sizeof(int), ctx->stream));
-  hipLaunchKernelGGL(ha_init_kernel, dim3(B), dim3(256), 0, ctx->stream, D, Q, B, dstart);
-  MP_HIP(ctx, hipGetLastError());
-  // The whole search loop is enqueued without host round trips: iteration i = one ha_step_kernel
-  // (RS_connected + 62 neighbours of every live scene, the bookkeeping + the next pop by the scene's
-  // last neighbour-group block, beside RS_connected; the finisher publishes or undoes).  live[i] (scenes
-  // still searching after iteration i) is copied back once per chunk of CH iterations; the host stays
-  // at most two chunks ahead of the device and stops enqueueing when a copied count is 0 (at most
-  // every scene's max_pops iterations).  (Round 1 fused the bookkeeping behind an agent-scope release
-  // in every block -- an L2 write-back each -- and measured 67-90 ms vs 40 ms; ha_step_kernel hands
-  // its records over with agent-coherent stores instead, so no block writes back its L2.)
-  constexpr int CH = 16;  // iterations per live-count poll
-  constexpr int NCK = 4;
-  int* hl = (int*)mp_pinned(ctx, sizeof(int) * NCK);
-  if (!hl) return mp_fail(ctx, MP_ERR_NOMEM, "pinned allocation failed");
-  hipEvent_t ev[NCK];
-  for (int i = 0; i < NCK; i++) MP_HIP(ctx, hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
-  auto cleanup = [&] { for (int i = 0; i < NCK; i++) hipEventDestroy(ev[i]); };
-  const int per = 1 + (np + NBG - 1) / NBG, per_tail = 1 + (np + NBG_TAIL - 1) / NBG_TAIL;
-  // the tail's rs_heuristic word units (ha_iter_body RSH): group g·4 + c holds neighbours 16g.. and word chunk
-  // c, so there must be a group for every (16-neighbour set, chunk) -- n_prim mod 16 in {0, 13, 14, 15} with
-  // 4 neighbours per group (62: yes); otherwise the groups' own word search.
-  const bool tail_rsh = HA_TAIL_RSH && NBG_TAIL == 4 && per_tail - 1 >= 4 * ((np + 15) / 16);
-  A.hp_c = (double*)mp_ws(ctx, WS_IO11, sizeof(double) * nB * np * 4 * NPAR);
-  A.hp_i = (int*)mp_ws(ctx, WS_IO12, sizeof(int) * nB * np * 4 * NPAR);
-  A.hp_t = (double*)mp_ws(ctx, WS_IO14, sizeof(double) * nB * np * 12 * NPAR);
-  const bool tail_pipe = tail_rsh;
-  // the persistent tail (ha_persist_kernel): one cooperative launch for the rest of the search once every block
-  // of it fits the device at once.  Without cooperative launches (or when one is refused) the tail runs one
-  // ha_pipe_kernel launch per iteration; MPGPU_HA_PERSIST=0 selects that fallback (a test hook: the same
-  // results, tests/test_gpu_hastar.py runs it)
-  const bool persist_env = !getenv("MPGPU_HA_PERSIST") || atoi(getenv("MPGPU_HA_PERSIST")) != 0;
-  int persist_cap = 0;
-  // the persistent kernel's block: 12 waves (one per CU: 14 scenes per launch), 6 (two per CU: 28 scenes; the
-  // groups' sweep on 3 waves beside the 3 word waves) or 4 (three per CU: 42 scenes; the sweep on one wave).
-  // Per call, the largest block that holds the whole batch in one launch from the start, and 6 when none does
-  // (the tail then starts at 28 live scenes).  Measured: a lone scenario 18.7 / 18.9 / 20.4 us per iteration
-  // with 12 / 6 / 4 (r05zg, r05zh); the 256-plan 24.0 ms with 6 or 4, 24.7 with 12; a 32-scene shard 16.4 ms with
-  // 4 against 18.4-20.1 with 6, whose tail starts only at 28 live scenes, two blocks sharing each CU.
-  const int per_ps = HA_PERSIST_PER((np + NBG_TAIL - 1) / NBG_TAIL);
-  const void* pfn_rs[3] = {reinterpret_cast<const void*>(ha_persist_kernel<HW_TAIL, NBG_TAIL>),
-                           reinterpret_cast<const void*>(ha_persist_kernel<6, NBG_TAIL>),
-                           reinterpret_cast<const void*>(ha_persist_kernel<4, NBG_TAIL>)};
-  const void* pfn_as[3] = {reinterpret_cast<const void*>(ha_persist_kernel<HW_TAIL, NBG_TAIL, HA_SPEC, true>),
-                           reinterpret_cast<const void*>(ha_persist_kernel<6, NBG_TAIL, HA_SPEC, true>),
-                           reinterpret_cast<const void*>(ha_persist_kernel<4, NBG_TAIL, HA_SPEC, true>)};
-  const void* const* pfn = use_astar ? pfn_as : pfn_rs;  // (the use_astar instances look the table up)
-  const int phws[3] = {HW_TAIL, 6, 4};
-  int* pcap = use_astar ? ctx->ha_pcap_ast : ctx->ha_pcap;  // co-resident blocks of each on this context's device (0: no cooperative launch)
-  int phw = 6;
-  const void* persist_fn = pfn[1];
-  double* rs_path2 = nullptr;
-  int* rs_i2 = nullptr;
-  if (tail_pipe && persist_env) {
-    if (pcap[0] < 0) {
-      int cus = 0, coop = 0;
-      const bool ok = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) == hipSuccess &&
-                      hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, ctx->device) == hipSuccess && coop;
-      for (int v = 0; v < 3; v++) {
-        int nbpc = 0;
-        pcap[v] = ok && hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbpc, pfn[v], 64 * phws[v], 0) == hipSuccess
-                      ? nbpc * cus : 0;
-      }
-      (void)hipGetLastError();
-    }
-    int v = 1;
-    for (int c = 0; c < 3; c++)
-      if (B * per_ps <= pcap[c]) { v = c; break; }
-    phw = phws[v];
-    persist_fn = pfn[v];
-    persist_cap = pcap[v];
-    // RS_connected's outputs by slot (ha_persist_kernel rs_slot): NPAR slots of rs_path, rs_ok (bytes), rs_len
-    rs_path2 = (double*)mp_ws(ctx, WS_IO15, sizeof(double) * NPAR * nB * MAXPATH * 3);
-    rs_i2 = (int*)mp_ws(ctx, WS_IO16, sizeof(int) * 2 * NPAR * nB);
-    if (!rs_path2 || !rs_i2) return MP_ERR_NOMEM;
-  }
-  bool persisted = false;
-  bool piped_any = false;  // an ha_pipe_kernel launch ran: its bounded waits report through Q.err too
-  // the pipelined launch's expansion blocks wait for their bookkeeping on a CU each: it pays only while the
-  // whole launch is resident at once (one 12-wave block per CU).  (Measured and removed: the full-width shape
-  // pipelined the same way, 0.4-0.9 ms slower per 256-plan, r05u/r05v: its bookkeeping publishes the pop ~10 us
-  // after its start, so pop + expansion is no shorter than expansion + the whole bookkeeping.)
-  constexpr int pipe_blocks = 256;
-  int piped = 0;  // the format of the records the last launch left in E[it & 1]: 0 none, 2 tail
+  A.hp_c = (double*)mp_ws(ctx, WS_IO11, sizeof(double) * nB * np * 4 * HA_NPAR);
+  A.hp_i = (int*)mp_ws(ctx, WS_IO12, sizeof(int) * nB * np * 4 * HA_NPAR);
+  A.hp_t = (double*)mp_ws(ctx, WS_IO14, sizeof(double) * nB * np * 12 * HA_NPAR);
+  if (!A.hp_c || !A.hp_i || !A.hp_t) return MP_ERR_NOMEM;
   // the prescan block only marks its record stale and takes its ticket (merging its PRE_K least entries into
   // popfirst! measured slower, r05j: 26.6 vs 25.7 us per lone iteration)
   A.no_pre = true;
@@ -4102,213 +4259,34 @@ int mp_ha_plan_astar(mp_ctx* ctx, const mp_ha_params* p, int32_t B, const double
   A.ngr_pub = true;  // the popped node handed over as tagged granules (r05zl)
   // (the full-width groups storing their winners' (t, u, v) too measured neutral per plan,
   // profiles/r05u_ha_fulltuv_mirror_fpipe_ab.txt)
-  if (!A.hp_c || !A.hp_i || !A.hp_t) return MP_ERR_NOMEM;
-  // iteration it >= 2 works on the compact list of scenes still live (written by the previous
-  // bookkeeping launch, count on the device); the host sizes the grids by the last live count it has
-  // seen (an upper bound: it only decreases) and switches to the tail shape once that many scenes
-  // fit in about two blocks per CU
-#ifndef HA_TAIL_BLOCKS
-#define HA_TAIL_BLOCKS 256
-#endif
-#ifndef HA_MID_BLOCKS
-#define HA_MID_BLOCKS 512
-#endif
-  // the middle shape: HA_MID_HW-wave blocks, 16 neighbours each (5 blocks per scene), once known * 5 fits in
-  // HA_MID_BLOCKS blocks.  r05x: the 6-wave middle shape for 16..102 live scenes and the tail from 15 (its
-  // pipelined / persistent forms from 14) -- 256-plan 25.6 -> 24.9 ms, the largest strided / contiguous shard
-  // 21.0 -> 19.2 / 17.9 -> 17.6 ms (the 12-wave tail step from 30 live scenes, round 4's threshold, and no middle)
-  constexpr int tail_blocks = HA_TAIL_BLOCKS;
-  constexpr int mid_blocks = HA_MID_BLOCKS;
-  int known = B;
-  int chunk = 0, checked = 0;
-  bool finished = false;
   // (Measured and removed: a live-count mirror in host memory written by every launch, 1.1-1.4 ms slower per
   // 256-plan, r05u/r05v -- each launch's system-scope store delays its end.)
   A.mirror = nullptr;
-  for (int it = 1; it <= mp && !finished; it++) {
-    A.scene_of = it == 1 ? nullptr : Q.lst + ((it - 1) & 1) * B;
-    A.n_live = it == 1 ? nullptr : Q.live + (it - 1);
-    A.n_active = known;
-    A.node = Q.node + (size_t)((it - 1) & 1) * 3 * B;  // the previous iteration's pops
-    A.node_rw = Q.node_rw + (size_t)((it - 1) & 1) * B;
-    A.node_tuv = Q.node_tuv + (size_t)((it - 1) & 1) * 3 * B;
-    const bool tail = known * per_tail <= tail_blocks;
-    if (tail_pipe && known * per_ps <= persist_cap) {
-      // the rest of the search in one cooperative launch, after the current nodes' expansion (bootstrap)
-      const int per_pipe = 2 + (np + NBG_TAIL - 1) / NBG_TAIL;
-      if (piped != 2) {
-        if (use_astar)
-          hipLaunchKernelGGL((ha_pipe_kernel<HW_TAIL, NBG_TAIL, true>), dim3((unsigned)(known * per_pipe)), dim3(64 * HW_TAIL),
-                             0, ctx->stream, D, Q, A, B, it, 1);
-        else
-          hipLaunchKernelGGL((ha_pipe_kernel<HW_TAIL, NBG_TAIL>), dim3((unsigned)(known * per_pipe)), dim3(64 * HW_TAIL),
-                             0, ctx->stream, D, Q, A, B, it, 1);
-        piped = 2;
-        piped_any = true;
-      }
-      unsigned char* rs_ok2 = reinterpret_cast<unsigned char*>(rs_i2);
-      int* rs_len2 = rs_i2 + NPAR * nB;
-      int it0 = it;
-      void* args[] = {&D, &Q, &A, (void*)&B, &it0, &rs_path2, &rs_ok2, &rs_len2};
-      // (MPGPU_HA_COOP=0: an ordinary launch of the same grid, co-resident by the occupancy check alone -- for
-      // rocprofv3 runs: the profiler's exit handlers crash in a process that made a cooperative launch)
-      static const bool coop_env = !getenv("MPGPU_HA_COOP") || atoi(getenv("MPGPU_HA_COOP")) != 0;
-      const hipError_t le =
-          coop_env ? hipLaunchCooperativeKernel(persist_fn, dim3((unsigned)(known * per_ps)), dim3(64 * phw), args, 0,
-                                                ctx->stream)
-                   : hipLaunchKernel(persist_fn, dim3((unsigned)(known * per_ps)), dim3(64 * phw), args, 0, ctx->stream);
-      if (le != hipSuccess) {
-        // refused (e.g. the device's co-residency changed under this context): the per-iteration pipelined
-        // tail from this iteration on -- the bootstrap above already expanded the current nodes
-        (void)hipGetLastError();
-        persist_cap = 0;
-        pcap[0] = pcap[1] = pcap[2] = 0;
-        it--;
-        continue;
-      }
-      persisted = true;
-      break;
-    } else if (tail && tail_pipe && known * (2 + (np + NBG_TAIL - 1) / NBG_TAIL) <= pipe_blocks) {
-      const int per_pipe = 2 + (np + NBG_TAIL - 1) / NBG_TAIL;
-      if (piped != 2) {  // the current nodes' expansion, for the first pipelined launch
-        if (use_astar)
-          hipLaunchKernelGGL((ha_pipe_kernel<HW_TAIL, NBG_TAIL, true>), dim3((unsigned)(known * per_pipe)), dim3(64 * HW_TAIL),
-                             0, ctx->stream, D, Q, A, B, it, 1);
-        else
-          hipLaunchKernelGGL((ha_pipe_kernel<HW_TAIL, NBG_TAIL>), dim3((unsigned)(known * per_pipe)), dim3(64 * HW_TAIL),
-                             0, ctx->stream, D, Q, A, B, it, 1);
-        piped = 2;
-      }
-      if (use_astar)
-        hipLaunchKernelGGL((ha_pipe_kernel<HW_TAIL, NBG_TAIL, true>), dim3((unsigned)(known * per_pipe)), dim3(64 * HW_TAIL), 0,
-                           ctx->stream, D, Q, A, B, it, 0);
-      else
-        hipLaunchKernelGGL((ha_pipe_kernel<HW_TAIL, NBG_TAIL>), dim3((unsigned)(known * per_pipe)), dim3(64 * HW_TAIL), 0,
-                           ctx->stream, D, Q, A, B, it, 0);
-      piped_any = true;
-    } else if (tail) {
-      piped = 0;
-      if (tail_rsh)  // + the prescan block per scene
-        if (use_astar)
-          hipLaunchKernelGGL((ha_step_kernel<HW_TAIL, NBG_TAIL, true, true>), dim3((unsigned)(known * (per_tail + 1))),
-                             dim3(64 * HW_TAIL), 0, ctx->stream, D, Q, A, B, it);
-        else
-          hipLaunchKernelGGL((ha_step_kernel<HW_TAIL, NBG_TAIL, true>), dim3((unsigned)(known * (per_tail + 1))),
-                             dim3(64 * HW_TAIL), 0, ctx->stream, D, Q, A, B, it);
-      else
-        if (use_astar)
-          hipLaunchKernelGGL((ha_step_kernel<HW_TAIL, NBG_TAIL, false, true>), dim3((unsigned)(known * per_tail)),
-                             dim3(64 * HW_TAIL), 0, ctx->stream, D, Q, A, B, it);
-        else
-          hipLaunchKernelGGL((ha_step_kernel<HW_TAIL, NBG_TAIL>), dim3((unsigned)(known * per_tail)),
-                             dim3(64 * HW_TAIL), 0, ctx->stream, D, Q, A, B, it);
-    } else if (known * per <= mid_blocks) {
-      piped = 0;
-      if (use_astar)
-        hipLaunchKernelGGL((ha_step_kernel<HA_MID_HW, NBG, false, true>), dim3((unsigned)(known * per)),
-                           dim3(64 * HA_MID_HW), 0, ctx->stream, D, Q, A, B, it);
-      else
-        hipLaunchKernelGGL((ha_step_kernel<HA_MID_HW, NBG>), dim3((unsigned)(known * per)),
-                           dim3(64 * HA_MID_HW), 0, ctx->stream, D, Q, A, B, it);
-    } else {
-      piped = 0;
-      if (use_astar)
-        hipLaunchKernelGGL((ha_step_kernel<HW, NBG, false, true>), dim3((unsigned)(known * per)), dim3(HT), 0,
-                           ctx->stream, D, Q, A, B, it);
-      else
-        hipLaunchKernelGGL((ha_step_kernel<HW, NBG>), dim3((unsigned)(known * per)), dim3(HT), 0,
-                           ctx->stream, D, Q, A, B, it);
-    }
-    if (hipGetLastError() != hipSuccess) { cleanup(); return mp_fail(ctx, MP_ERR_HIP, "ha kernel launch failed"); }
-    // (Measured and removed: polling the live count every 4 iterations near the persistent tail's threshold,
-    // 1 ms slower per 256-plan, r05zn.)
-    if (it % CH == 0 || it == mp) {
-      const int slot = chunk % NCK;
-      if (hipMemcpyAsync(hl + slot, Q.live + it, sizeof(int), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-          hipEventRecord(ev[slot], ctx->stream) != hipSuccess) {
-        cleanup();
-        return mp_fail(ctx, MP_ERR_HIP, "live-count copy failed");
-      }
-      chunk++;
-      // poll finished chunks without blocking; block only when two chunks ahead
-      while (checked < chunk) {
-        const int cs = checked % NCK;
-        const bool must = chunk - checked > 2;
-        const hipError_t q = must ? hipEventSynchronize(ev[cs]) : hipEventQuery(ev[cs]);
-        if (q == hipErrorNotReady) break;
-        if (q != hipSuccess) { cleanup(); return mp_fail(ctx, MP_ERR_HIP, "event wait failed"); }
-        if (hl[cs] == 0) { finished = true; break; }
-        known = std::min(known, std::max(hl[cs], 1));
-        checked++;
-      }
-    }
-  }
+  MP_HIP(ctx, hipMemsetAsync(Q.pop_seq, 0xff, nB * mp * 8, ctx->stream));  // -1 past each scene's pops
+  MP_HIP(ctx, hipMemsetAsync(Q.live, 0, sizeof(int) * (mp + 2), ctx->stream));
+  MP_HIP(ctx, hipMemsetAsync(Q.tk, 0, sizeof(int) * 2 * nB, ctx->stream));  // the finishers reset them
+  MP_HIP(ctx, hipMemsetAsync(Q.rec, 0, sizeof(long long) * RC_N * nB, ctx->stream));  // record-ready flags
+  MP_HIP(ctx, hipMemsetAsync(Q.nx, 0, sizeof(int) * nB, ctx->stream));  // ha_pipe_kernel's pop flags
+  MP_HIP(ctx, hipMemsetAsync(Q.ngr, 0, sizeof(unsigned long long) * nB * HA_NGR_SLOTS * HA_NGR, ctx->stream));  // granule tags
+  MP_HIP(ctx, hipMemsetAsync(Q.ex, 0, sizeof(int) * nB, ctx->stream));  // ha_persist_kernel's flags
+  MP_HIP(ctx, hipMemsetAsync(Q.rsr, 0, sizeof(int) * 2 * nB, ctx->stream));
+  MP_HIP(ctx, hipMemsetAsync(Q.ngr2, 0, sizeof(unsigned long long) * nB * HA_NGR_SLOTS * HA_NGR, ctx->stream));  // (the runner-up's)
+  MP_HIP(ctx, hipMemsetAsync(Q.exs, 0, sizeof(int) * 2 * nB, ctx->stream));
+  MP_HIP(ctx, hipMemsetAsync(Q.rsrs, 0, sizeof(int) * 2 * nB, ctx->stream));
+  MP_HIP(ctx, hipMemsetAsync(Q.nhit, 0, sizeof(int) * 2 * nB, ctx->stream));
+  MP_HIP(ctx, hipMemsetAsync(Q.err, 0, sizeof(int), ctx->stream));
+  hipLaunchKernelGGL(ha_init_kernel, dim3(B), dim3(256), 0, ctx->stream, D, Q, B, dstart);
+  MP_HIP(ctx, hipGetLastError());
+  HaEvents ev;  // (outlives the read-back's last synchronisation)
+  for (int i = 0; i < HA_NCK; i++) MP_HIP(ctx, hipEventCreateWithFlags(&ev.e[i], hipEventDisableTiming));
+  bool persisted = false, waited = false;
+  if ((st = ha_search_loop(ctx, D, Q, A, B, use_astar != 0, ev, &persisted, &waited))) return st;
   // -1 past every scene's pops, filled while the search still runs on the device: the copy after it
   // overwrites columns [0, max_loop) (the device's memset padded those)
   std::fill(pop_seq, pop_seq + nB * mp, (int64_t)-1);
-  if (A.stamps) {  // diagnostics: raw stamps to $MPGPU_HA_STAMPS_OUT (tools/ha_stamps.py reads them)
-    std::vector<unsigned long long> h((size_t)HA_STAMP_N * stamp_slots * A.stamp_blocks);
-    MP_HIP(ctx, hipMemcpyAsync(h.data(), A.stamps, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-    MP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const char* fn = getenv("MPGPU_HA_STAMPS_OUT");
-    if (FILE* f = fopen(fn ? fn : "ha_stamps.bin", "wb")) {
-      const long long hdr[5] = {B, stamp_slots, A.stamp_blocks, HA_STAMP_EVERY, HA_STAMP_N};
-      fwrite(hdr, sizeof hdr, 1, f);
-      fwrite(h.data(), 8, h.size(), f);
-      fclose(f);
-    }
-  }
-  if (persisted || piped_any) {  // a bounded wait (persistent or pipelined launch) that ran out: not trusted
-    int err = 0;
-    if (hipMemcpyAsync(&err, Q.err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-        hipStreamSynchronize(ctx->stream) != hipSuccess) {
-      cleanup();
-      return mp_fail(ctx, MP_ERR_HIP, "persistent search failed");
-    }
-    if (err) { cleanup(); return mp_fail(ctx, MP_ERR_HIP, "Hybrid A* search: a cross-block wait timed out"); }
-  }
-  if (getenv("MPGPU_HA_SPEC_STATS")) {  // diagnostics: how often the speculative runner-up was the next pop
-    std::vector<int> nh(2 * nB);
-    MP_HIP(ctx, hipMemcpyAsync(nh.data(), Q.nhit, sizeof(int) * 2 * nB, hipMemcpyDeviceToHost, ctx->stream));
-    MP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    long long hits = 0, pubs = 0;
-    for (size_t i = 0; i < nB; i++) { hits += nh[i]; pubs += nh[nB + i]; }
-    fprintf(stderr, "[ha spec] persisted %d: runner-ups published %lld, pops that were the runner-up %lld\n",
-            (int)persisted, pubs, hits);
-  }
-  // outputs: per-scene counters, then the used prefix of pop_seq / states / RS paths
-  std::vector<int> si(SI_N * nB);
-  if ((st = mp_download(ctx, si.data(), (const int*)Q.sc_i, SI_N * nB))) { cleanup(); return st; }
-  if (hipStreamSynchronize(ctx->stream) != hipSuccess) { cleanup(); return mp_fail(ctx, MP_ERR_HIP, "search failed"); }
-  cleanup();
-  int max_loop = 0, max_ns = 0, max_rs = 0;
-  for (int b = 0; b < B; b++) {
-    found[b] = si[SI_FOUND * B + b];
-    pops[b] = si[SI_LOOP * B + b];
-    n_nodes[b] = si[SI_NNODES * B + b];
-    n_states[b] = si[SI_NSTATES * B + b];
-    rs_len[b] = found[b] ? si[SI_RSLEN * B + b] : 0;
-    max_loop = std::max(max_loop, pops[b]);
-    max_ns = std::max(max_ns, n_states[b]);
-    max_rs = std::max(max_rs, rs_len[b]);
-  }
-  if (max_loop > 0)
-    MP_HIP(ctx, hipMemcpy2DAsync(pop_seq, sizeof(int64_t) * mp, Q.pop_seq, sizeof(long long) * mp,
-                                 sizeof(long long) * max_loop, nB, hipMemcpyDeviceToHost, ctx->stream));
-  if (max_ns > 0)
-    MP_HIP(ctx, hipMemcpy2DAsync(states_out, sizeof(double) * 3 * mp, Q.states, sizeof(double) * 3 * mp,
-                                 sizeof(double) * 3 * max_ns, nB, hipMemcpyDeviceToHost, ctx->stream));
-  std::vector<double> rsb;
-  if (max_rs > 0) {
-    rsb.resize(nB * max_rs * 3);
-    MP_HIP(ctx, hipMemcpy2DAsync(rsb.data(), sizeof(double) * 3 * max_rs, A.rs_path, sizeof(double) * 3 * MAXPATH,
-                                 sizeof(double) * 3 * max_rs, nB, hipMemcpyDeviceToHost, ctx->stream));
-  }
-  MP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  for (int b = 0; b < B; b++)
-    if (found[b])
-      std::copy(rsb.begin() + (size_t)b * max_rs * 3, rsb.begin() + ((size_t)b * max_rs + rs_len[b]) * 3,
-                rs_path + (size_t)b * MAXPATH * 3);
+  if ((st = ha_read_back(ctx, Q, A, B, stamp_slots, persisted, waited, found, pops, n_nodes, pop_seq, n_states,
+                         states_out, rs_len, rs_path)))
+    return st;
   return use_astar ? mp_as_table_status(ctx) : MP_OK;
 }
 

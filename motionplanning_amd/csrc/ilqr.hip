@@ -56,118 +56,34 @@ struct UPre {  // control-only part of Dynamics (Dynamics.jl:8-12)
   double tdl, beta, cb;
 };
 
-// libm policy.  LM<true>: straight-line FDLIBM cores (include/mp_jlmath.h *_fast): no branch
-// at all, so a whole knot is one basic block the scheduler can interleave; a lane whose
-// argument leaves a core's fast range sets `bad`, and the kernel then re-runs that unit of
-// work (knot / sweep / trial) for the wave with LM<false>, the exact branchy routines.  The
-// cores equal the exact routines bit for bit on their fast range (tests/test_jlmath.py).
-template <bool F> struct LM;
-// A/B builds: -DMP_ILQR_EXACT (exact libm only), -DMP_ILQR_NOREDO (timing only: no fallback)
-#if defined(MP_ILQR_EXACT)
-constexpr bool kFast = false;
-#else
-constexpr bool kFast = true;
-#endif
-// Per kernel (measured, gfx950, configs[2]): the straight-line cores pay off only in the Riccati
-// sweep (355 vs 382 us).  The derivative kernel (405,504 threads, lanes of a wave take the same
-// libm branches) runs the exact routines in 154 us vs 296 us, and the one-thread-per-instance
-// forward trial / roll out (64 waves, latency-bound: fewer instructions win) in 361 vs 690 us.
-// A/B (-DMP_ILQR_FASTSC): the forward trial / roll out's four RK4 stage sincos on the
-// straight-line core (rk4_ilp, independent of each other) with an exact redo for arguments out
-// of range.  Measured slower: forward 386 vs 361 us, roll out 356 vs 276 us (a lone wave is
-// issue-limited: the straight-line core's extra instructions cost more than the overlap gains).
-#if defined(MP_ILQR_NOQUAD) || defined(MP_ILQR_FASTFWD)
-constexpr bool kFwdQuad = false;
-#else
-constexpr bool kFwdQuad = true;  // ilqr_forward_quad_kernel: a lane quad per instance
-#ifndef ILQR_SEARCH_L
-#define ILQR_SEARCH_L 4
-#endif
-constexpr int kSearchL = ILQR_SEARCH_L;  // lanes per line-search trial in mp_ilqr_solve (1 or 4)
-#ifndef ILQR_ROUND0_L
-#define ILQR_ROUND0_L 2
-#endif
-constexpr int kRound0L = ILQR_ROUND0_L;  // lanes per trial in the pipelined launch's round 0 (2 or 4) ...
-#ifndef ILQR_PAIR_MIN
-#define ILQR_PAIR_MIN 2048
-#endif
-constexpr int kPairMin = ILQR_PAIR_MIN;  // ... while at least this many instances are active (else 4)
-#ifndef ILQR_ONEPASS_MAX
-#define ILQR_ONEPASS_MAX 512
-#endif
-constexpr int kOnePassMax = ILQR_ONEPASS_MAX;  // active instances up to which the search is one pass
-#ifndef ILQR_PIPE
-#define ILQR_PIPE 1
-#endif
-constexpr bool kPipe = ILQR_PIPE;  // overlap each rest pass with the next iteration's round 0
-#ifndef ILQR_DERIV4_MAX
-#define ILQR_DERIV4_MAX 2048
-#endif
-constexpr int kDeriv4Max = ILQR_DERIV4_MAX;  // derivative launches for at most this many instances: 4 lanes each
-#ifndef ILQR_SEARCH_G
-#define ILQR_SEARCH_G 16
-#endif
-constexpr int kSearchG = ILQR_SEARCH_G;  // trials per instance in the first round (a power of two <= 16)
-#endif
-#if defined(MP_ILQR_FASTSC)
-constexpr bool kFastSC = true;
-#else
-constexpr bool kFastSC = false;
-#endif
-#if defined(MP_ILQR_FASTFWD)  // A/B build (measured slower: forward 689 vs 363 us, roll out 341 vs 277 us)
-constexpr bool kFastDeriv = false, kFastBwd = kFast, kFastFwd = kFast;
-#else
-constexpr bool kFastDeriv = false, kFastBwd = kFast, kFastFwd = false;
-#endif
-#if defined(MP_ILQR_NOREDO)
-constexpr bool kRedo = false;
-#else
-constexpr bool kRedo = true;
-#endif
-#if defined(MP_ILQR_BADSTAT)  // diagnostics build: print arguments that leave a core's range
-__device__ int g_nbad = 0;
-#endif
-template <> struct LM<true> {
-#if !defined(MP_ILQR_BADSTAT)
-  static __device__ __forceinline__ double tan(double x, int& b) { return mpj_tan_wide(x, &b); }
-  static __device__ __forceinline__ double atan(double x, int&) { return mpj_atan_bl(x); }
-  static __device__ __forceinline__ void sincos(double x, double* s, double* c, int& b) { mpj_sincos_wide(x, s, c, &b); }
-  // Julia's table-driven exp is one basic block for |x| <= 708.39 (the far branch is wave-uniform here)
-  static __device__ __forceinline__ double exp(double x, int&) { return mpj_exp(x); }
-  static __device__ __forceinline__ double atan2(double y, double x, int& b) { return mpj_atan2_fast(y, x, &b); }
-#else
-  static __device__ double tan(double x, int& b) { int t = 0; double r = mpj_tan_wide(x, &t); if (t) { b |= 1; if (atomicAdd(&g_nbad, 1) < 8) printf("tan %.17g\n", x); } return r; }
-  static __device__ double atan(double x, int&) { return mpj_atan_bl(x); }
-  static __device__ void sincos(double x, double* s, double* c, int& b) { int t = 0; mpj_sincos_wide(x, s, c, &t); if (t) { b |= 2; if (atomicAdd(&g_nbad, 1) < 8) printf("sincos %.17g\n", x); } }
-  static __device__ double exp(double x, int&) { return mpj_exp(x); }
-  static __device__ double atan2(double y, double x, int& b) { int t = 0; double r = mpj_atan2_fast(y, x, &t); if (t) { b |= 8; if (atomicAdd(&g_nbad, 1) < 8) printf("atan2 %.17g %.17g\n", y, x); } return r; }
-#endif
-};
-template <> struct LM<false> {
-  static __device__ __forceinline__ double tan(double x, int&) { return mpj_tan(x); }
-  static __device__ __forceinline__ double atan(double x, int&) { return mpj_atan(x); }
-  static __device__ __forceinline__ void sincos(double x, double* s, double* c, int&) { mpj_sincos(x, s, c); }
-  static __device__ __forceinline__ double exp(double x, int&) { return mpj_exp(x); }
-  static __device__ __forceinline__ double atan2(double y, double x, int&) { return mpj_atan2(y, x); }
-};
+// libm: the exact FDLIBM routines of include/mp_jlmath.h (mpj_tan, mpj_atan, mpj_sincos, mpj_exp) in every
+// kernel.  (Measured, gfx950, configs[2]: the derivative kernel -- 405,504 threads, lanes of a wave take the same
+// libm branches -- runs them in 154 us against 296 us with the straight-line *_wide cores and an exact redo, the
+// one-thread-per-instance forward trial / roll out -- 64 waves, latency-bound: fewer instructions win -- in 361
+// against 690 us, and with only the four RK4 stage sincos on the straight-line core in 361 / 276 against
+// 386 / 356 us.)
+constexpr int kSearchL = 4;        // lanes per line-search trial in mp_ilqr_solve (1 or 4)
+constexpr int kRound0L = 2;        // lanes per trial in the pipelined launch's round 0 (2 or 4) ...
+constexpr int kPairMin = 2048;     // ... while at least this many instances are active (else 4)
+constexpr int kOnePassMax = 512;   // active instances up to which the search is one pass
+constexpr int kDeriv4Max = 2048;   // derivative launches for at most this many instances: 4 lanes each
+constexpr int kSearchG = 16;       // trials per instance in the first round (a power of two <= 16)
 
-template <bool F>
-__device__ __forceinline__ UPre upre(double dl, int& bad) {
+__device__ __forceinline__ UPre upre(double dl) {
   const double la = 1.56, lb = 1.64;
   UPre q;
-  q.tdl = LM<F>::tan(dl, bad);
-  q.beta = LM<F>::atan(la / (la + lb) * q.tdl, bad);
+  q.tdl = mpj_tan(dl);
+  q.beta = mpj_atan(la / (la + lb) * q.tdl);
   double sb;
-  LM<F>::sincos(q.beta, &sb, &q.cb, bad);  // cos β (the cos of sincos == mpj_cos bit for bit)
+  mpj_sincos(q.beta, &sb, &q.cb);  // cos β (the cos of sincos == mpj_cos bit for bit)
   return q;
 }
 
 // Dynamics.jl:1-16
-template <bool F>
-__device__ __forceinline__ void dyn(const double* s, double ax, const UPre& q, double* d, int& bad) {
+__device__ __forceinline__ void dyn(const double* s, double ax, const UPre& q, double* d) {
   const double la = 1.56, lb = 1.64;
   double sb, cbb;
-  LM<F>::sincos(s[3] + q.beta, &sb, &cbb, bad);
+  mpj_sincos(s[3] + q.beta, &sb, &cbb);
   d[0] = s[2] * cbb;
   d[1] = s[2] * sb;
   d[2] = ax;
@@ -177,26 +93,24 @@ __device__ __forceinline__ void dyn(const double* s, double ax, const UPre& q, d
 // RK4Integration, Dynamics.jl:18-28, as its increment: o[i] = inc[i] + s[i] with
 // inc[i] = 1/6·(k1 + 2k2 + 2k3 + k4)·dT.  dyn reads only s[2] (speed) and s[3] (heading), so the
 // stage slopes -- and inc -- do not depend on s[0] / s[1] at all (knot_derivs uses that).
-template <bool F>
-__device__ __forceinline__ void rk4_inc(const double* s, double ax, const UPre& q, double dT, double* inc, int& bad) {
+__device__ __forceinline__ void rk4_inc(const double* s, double ax, const UPre& q, double dT, double* inc) {
   double k1[4], k2[4], k3[4], k4[4], x2[4], x3[4], x4[4];
-  dyn<F>(s, ax, q, k1, bad);
+  dyn(s, ax, q, k1);
 #pragma unroll
   for (int i = 0; i < 4; i++) x2[i] = s[i] + dT / 2 * k1[i];
-  dyn<F>(x2, ax, q, k2, bad);
+  dyn(x2, ax, q, k2);
 #pragma unroll
   for (int i = 0; i < 4; i++) x3[i] = s[i] + dT / 2 * k2[i];
-  dyn<F>(x3, ax, q, k3, bad);
+  dyn(x3, ax, q, k3);
 #pragma unroll
   for (int i = 0; i < 4; i++) x4[i] = s[i] + dT * k3[i];
-  dyn<F>(x4, ax, q, k4, bad);
+  dyn(x4, ax, q, k4);
 #pragma unroll
   for (int i = 0; i < 4; i++) inc[i] = 1.0 / 6 * (k1[i] + 2 * k2[i] + 2 * k3[i] + k4[i]) * dT;
 }
-template <bool F>
-__device__ __forceinline__ void rk4(const double* s, double ax, const UPre& q, double dT, double* o, int& bad) {
+__device__ __forceinline__ void rk4(const double* s, double ax, const UPre& q, double dT, double* o) {
   double inc[4];
-  rk4_inc<F>(s, ax, q, dT, inc, bad);
+  rk4_inc(s, ax, q, dT, inc);
 #pragma unroll
   for (int i = 0; i < 4; i++) o[i] = inc[i] + s[i];
 }
@@ -204,9 +118,9 @@ __device__ __forceinline__ void rk4(const double* s, double ax, const UPre& q, d
 // stages 1-2 written to sc).  knot_derivs' RK4s of the knot's own state, of its speed ± eps and of
 // ax ± eps have bit-identical stage-1 headings s[3] + β, and the ax pair also the stage-2 heading
 // (ax enters only the speed slope k[2]): the same sincos on the same argument, evaluated once.
-template <bool F, int NS>
+template <int NS>
 __device__ __forceinline__ void rk4_inc_sh(const double* s, double ax, const UPre& q, double dT, double* inc,
-                                           int& bad, double (&sc)[2][2]) {
+                                           double (&sc)[2][2]) {
   const double la = 1.56, lb = 1.64;
   double k[4][4], xs[4];
 #pragma unroll
@@ -217,7 +131,7 @@ __device__ __forceinline__ void rk4_inc_sh(const double* s, double ax, const UPr
       sn = sc[st][0];
       cs = sc[st][1];
     } else {
-      LM<F>::sincos(xi[3] + q.beta, &sn, &cs, bad);
+      mpj_sincos(xi[3] + q.beta, &sn, &cs);
       if (NS == 0 && st < 2) {
         sc[st][0] = sn;
         sc[st][1] = cs;
@@ -255,21 +169,18 @@ __device__ __forceinline__ void dyn_jac_xy_inc(const double* s, const double* in
     for (int r = 0; r < 4; r++) out[(size_t)(4 * r + i) * stride] = ((inc[r] + sp[r]) - (inc[r] + sm[r])) / (2 * e);
   }
 }
-template <bool F>
 __device__ __forceinline__ void dyn_jac_xy(const double* s, double ax, const UPre& q, double dT, double e, double* out,
-                                           size_t stride, int& bad) {
+                                           size_t stride) {
   double inc[4];
-  rk4_inc<F>(s, ax, q, dT, inc, bad);
+  rk4_inc(s, ax, q, dT, inc);
   dyn_jac_xy_inc(s, inc, e, out, stride);
 }
 
 // RK4Integration with the four stage headings computed first.  The stage speed and heading
 // (dyn's d[2] = ax, d[3] = s2·cb·tδ/L) never depend on a sine or cosine, so the four stage
-// sincos are independent of each other: with the straight-line core (SC = true) the scheduler
-// overlaps them instead of running four dependent libm chains.  The same operations on the
-// same operands as rk4, so the same bits.
-template <bool SC>
-__device__ __forceinline__ void rk4_ilp(const double* s, double ax, const UPre& q, double dT, double* o, int& bad) {
+// sincos are independent of each other.  The same operations on the same operands as rk4, so the
+// same bits.
+__device__ __forceinline__ void rk4_ilp(const double* s, double ax, const UPre& q, double dT, double* o) {
   const double la = 1.56, lb = 1.64;
   const double k1_3 = s[2] * q.cb * q.tdl / (la + lb);
   const double x2_2 = s[2] + dT / 2 * ax, x2_3 = s[3] + dT / 2 * k1_3;
@@ -279,10 +190,10 @@ __device__ __forceinline__ void rk4_ilp(const double* s, double ax, const UPre& 
   const double x4_2 = s[2] + dT * ax, x4_3 = s[3] + dT * k3_3;
   const double k4_3 = x4_2 * q.cb * q.tdl / (la + lb);
   double s1, c1, s2, c2, s3, c3, s4, c4;
-  LM<SC>::sincos(s[3] + q.beta, &s1, &c1, bad);
-  LM<SC>::sincos(x2_3 + q.beta, &s2, &c2, bad);
-  LM<SC>::sincos(x3_3 + q.beta, &s3, &c3, bad);
-  LM<SC>::sincos(x4_3 + q.beta, &s4, &c4, bad);
+  mpj_sincos(s[3] + q.beta, &s1, &c1);
+  mpj_sincos(x2_3 + q.beta, &s2, &c2);
+  mpj_sincos(x3_3 + q.beta, &s3, &c3);
+  mpj_sincos(x4_3 + q.beta, &s4, &c4);
   const double k1[4] = {s[2] * c1, s[2] * s1, ax, k1_3};
   const double k2[4] = {x2_2 * c2, x2_2 * s2, ax, k2_3};
   const double k3[4] = {x3_2 * c3, x3_2 * s3, ax, k3_3};
@@ -292,19 +203,16 @@ __device__ __forceinline__ void rk4_ilp(const double* s, double ax, const UPre& 
 }
 
 // sigmoid_boundary, Cost.jl:42-49
-template <bool F>
-__device__ __forceinline__ double sigmoid_boundary(double st, double mn, double mx, int& bad) {
+__device__ __forceinline__ double sigmoid_boundary(double st, double mn, double mx) {
   const double slope = 10, mag = 100;
-  const double c1 = 1 / (1 + LM<F>::exp(-slope * (st - mx), bad));
-  const double c2 = 1 / (1 + LM<F>::exp(slope * (st - mn), bad));
+  const double c1 = 1 / (1 + mpj_exp(-slope * (st - mx)));
+  const double c2 = 1 / (1 + mpj_exp(slope * (st - mn)));
   return mag * (c1 + c2);
 }
-template <bool F>
-__device__ __forceinline__ double sig_d(double dl, int& bad) {
-  return sigmoid_boundary<F>(dl, -MPJ_PI / 6, MPJ_PI / 6, bad);
+__device__ __forceinline__ double sig_d(double dl) {
+  return sigmoid_boundary(dl, -MPJ_PI / 6, MPJ_PI / 6);
 }
-template <bool F>
-__device__ __forceinline__ double sig_a(double ax, int& bad) { return sigmoid_boundary<F>(ax, -2, 2, bad); }
+__device__ __forceinline__ double sig_a(double ax) { return sigmoid_boundary(ax, -2, 2); }
 
 // StageCost (Cost.jl:10-27 / Parking_ILQR/Cost.jl:21) with the barrier terms supplied
 __device__ __forceinline__ double stage_pre(int variant, const double* s, double ax, double dl, double sd,
@@ -315,9 +223,8 @@ __device__ __forceinline__ double stage_pre(int variant, const double* s, double
            0.01 * (ux * ux) + sd + sa;
   return 10 * (ax * ax) + 10 * (dl * dl) + 0.01 * (ux * ux) + sd + sa;
 }
-template <bool F>
-__device__ __forceinline__ double stage(int variant, const double* s, const double* u, int& bad) {
-  return stage_pre(variant, s, u[0], u[1], sig_d<F>(u[1], bad), sig_a<F>(u[0], bad));
+__device__ __forceinline__ double stage(int variant, const double* s, const double* u) {
+  return stage_pre(variant, s, u[0], u[1], sig_d(u[1]), sig_a(u[0]));
 }
 // TerminalCost, Cost.jl:29-40
 __device__ __forceinline__ double terminal(int variant, const double* s) {
@@ -329,8 +236,7 @@ __device__ __forceinline__ double terminal(int variant, const double* s) {
 
 __device__ double total_cost(int variant, int N, const double* X, const double* U) {  // exact libm
   double J = 0.0;
-  int bad = 0;
-  for (int i = 0; i < N - 1; i++) J = J + stage<false>(variant, X + 4 * i, U + 2 * i, bad);
+  for (int i = 0; i < N - 1; i++) J = J + stage(variant, X + 4 * i, U + 2 * i);
   return J + terminal(variant, X + 4 * (N - 1));
 }
 
@@ -349,27 +255,25 @@ __device__ __forceinline__ double cst(int variant, const double* s, const SigCac
 // component q goes to out[q * stride] (the record is component-major across instances, so
 // consecutive threads store consecutive doubles); every loop is unrolled so the perturbed
 // states stay in registers (no scratch).
-template <bool F>
 __device__ __forceinline__ void knot_cost_derivs(const IlqrDev& P, const double* s, const double* u, double* out,
-                                                 size_t stride, int& bad);
+                                                 size_t stride);
 // the dynamics Jacobians of knot_derivs (LocallyLinearizeDynamics, GetMatrix.jl:70-91): A, B
-template <bool F>
 __device__ __forceinline__ void knot_dyn_derivs(const IlqrDev& P, const double* s, const double* u, double* out,
-                                                size_t stride, int& bad) {
+                                                size_t stride) {
   const double e = P.eps;
 #define DOUT(q) out[(size_t)(q) * stride]
   // ---- dynamics Jacobians: A (row-major 4x4) at 0, B (4x2) at 16
-  const UPre q0 = upre<F>(u[1], bad);
+  const UPre q0 = upre(u[1]);
   double sp[4], sm[4], fp[4], fm[4], inc[4], incm[4], sc[2][2];
-  rk4_inc_sh<F, 0>(s, u[0], q0, P.dT, inc, bad, sc);  // the knot's own state: stage 1-2 sincos kept
+  rk4_inc_sh<0>(s, u[0], q0, P.dT, inc, sc);  // the knot's own state: stage 1-2 sincos kept
   dyn_jac_xy_inc(s, inc, e, out, stride);
   {  // speed ± eps: stage 1's heading is s[3]
 #pragma unroll
     for (int r = 0; r < 4; r++) { sp[r] = s[r]; sm[r] = s[r]; }
     sp[2] = s[2] + e;
     sm[2] = s[2] - e;
-    rk4_inc_sh<F, 1>(sp, u[0], q0, P.dT, inc, bad, sc);
-    rk4_inc_sh<F, 1>(sm, u[0], q0, P.dT, incm, bad, sc);
+    rk4_inc_sh<1>(sp, u[0], q0, P.dT, inc, sc);
+    rk4_inc_sh<1>(sm, u[0], q0, P.dT, incm, sc);
 #pragma unroll
     for (int r = 0; r < 4; r++) DOUT(4 * r + 2) = ((inc[r] + sp[r]) - (incm[r] + sm[r])) / (2 * e);
   }
@@ -378,35 +282,33 @@ __device__ __forceinline__ void knot_dyn_derivs(const IlqrDev& P, const double* 
     for (int r = 0; r < 4; r++) { sp[r] = s[r]; sm[r] = s[r]; }
     sp[3] = s[3] + e;
     sm[3] = s[3] - e;
-    rk4<F>(sp, u[0], q0, P.dT, fp, bad);
-    rk4<F>(sm, u[0], q0, P.dT, fm, bad);
+    rk4(sp, u[0], q0, P.dT, fp);
+    rk4(sm, u[0], q0, P.dT, fm);
 #pragma unroll
     for (int r = 0; r < 4; r++) DOUT(4 * r + 3) = (fp[r] - fm[r]) / (2 * e);
   }
   {  // ax perturbation leaves the δ-only terms unchanged (and stage 1-2 headings: rk4_inc_sh)
-    rk4_inc_sh<F, 2>(s, u[0] + e, q0, P.dT, inc, bad, sc);
-    rk4_inc_sh<F, 2>(s, u[0] - e, q0, P.dT, incm, bad, sc);
+    rk4_inc_sh<2>(s, u[0] + e, q0, P.dT, inc, sc);
+    rk4_inc_sh<2>(s, u[0] - e, q0, P.dT, incm, sc);
 #pragma unroll
     for (int r = 0; r < 4; r++) DOUT(16 + 2 * r + 0) = ((inc[r] + s[r]) - (incm[r] + s[r])) / (2 * e);
-    const UPre qp = upre<F>(u[1] + e, bad), qm = upre<F>(u[1] - e, bad);
-    rk4<F>(s, u[0], qp, P.dT, fp, bad);
-    rk4<F>(s, u[0], qm, P.dT, fm, bad);
+    const UPre qp = upre(u[1] + e), qm = upre(u[1] - e);
+    rk4(s, u[0], qp, P.dT, fp);
+    rk4(s, u[0], qm, P.dT, fm);
 #pragma unroll
     for (int r = 0; r < 4; r++) DOUT(16 + 2 * r + 1) = (fp[r] - fm[r]) / (2 * e);
   }
 #undef DOUT
 }
-template <bool F>
 __device__ __forceinline__ void knot_derivs(const IlqrDev& P, const double* s, const double* u, double* out,
-                                            size_t stride, int& bad) {
-  knot_dyn_derivs<F>(P, s, u, out, stride, bad);
-  knot_cost_derivs<F>(P, s, u, out, stride, bad);
+                                            size_t stride) {
+  knot_dyn_derivs(P, s, u, out, stride);
+  knot_cost_derivs(P, s, u, out, stride);
 }
 
 // the cost derivatives of knot_derivs (GetMatrix.jl CalculateMatrix): lx 24, lu 28, lxx 30, luu 46, lux 50
-template <bool F>
 __device__ __forceinline__ void knot_cost_derivs(const IlqrDev& P, const double* s, const double* u, double* out,
-                                                 size_t stride, int& bad) {
+                                                 size_t stride) {
   const double e = P.eps;
 #define DOUT(q) out[(size_t)(q) * stride]
   double sp[4], sm[4];
@@ -415,8 +317,8 @@ __device__ __forceinline__ void knot_cost_derivs(const IlqrDev& P, const double*
   C.d[0] = u[1] - 2 * e; C.d[1] = u[1] - e; C.d[2] = u[1]; C.d[3] = u[1] + e; C.d[4] = u[1] + 2 * e;
 #pragma unroll
   for (int t = 0; t < 5; t++) {
-    C.sa[t] = sig_a<F>(C.a[t], bad);
-    C.sd[t] = sig_d<F>(C.d[t], bad);
+    C.sa[t] = sig_a(C.a[t]);
+    C.sd[t] = sig_d(C.d[t]);
   }
   const int V = P.variant;
   const double c12 = 1 / (12 * (e * e)), c4 = 1 / (4 * (e * e));
@@ -493,12 +395,7 @@ __global__ __launch_bounds__(256) void ilqr_deriv_kernel(IlqrDev P, int B, const
   const double s[4] = {xs[0], xs[1], xs[2], xs[3]};
   const double u[2] = {us[0], us[1]};
   double* out = D + (size_t)j * ND * B + i;
-  int bad = 0;
-  knot_derivs<kFastDeriv>(P, s, u, out, (size_t)B, bad);
-  if (kFastDeriv && kRedo && __any(bad)) {  // some lane left a straight-line core's range: redo the wave exactly
-    int d = 0;
-    knot_derivs<false>(P, s, u, out, (size_t)B, d);
-  }
+  knot_derivs(P, s, u, out, (size_t)B);
 }
 
 // knot_derivs split four ways for the latency-bound launches (few active instances): parts 0-2
@@ -509,7 +406,6 @@ template <int PART>
 __device__ __forceinline__ void knot_derivs_part(const IlqrDev& P, const double* s, const double* u, double* out,
                                                  size_t stride) {
   const double e = P.eps;
-  int bad = 0;
 #define DOUT(q) out[(size_t)(q) * stride]
   // the dynamics Jacobian over three waves (RK4 counts 3 / 4 / 2 + the two perturbed upre)
   auto state_col = [&](int i, const UPre& q0) {  // column i of A: state i ± eps
@@ -518,32 +414,32 @@ __device__ __forceinline__ void knot_derivs_part(const IlqrDev& P, const double*
     for (int r = 0; r < 4; r++) { sp[r] = s[r]; sm[r] = s[r]; }
     sp[i] = s[i] + e;
     sm[i] = s[i] - e;
-    rk4<false>(sp, u[0], q0, P.dT, fp, bad);
-    rk4<false>(sm, u[0], q0, P.dT, fm, bad);
+    rk4(sp, u[0], q0, P.dT, fp);
+    rk4(sm, u[0], q0, P.dT, fm);
 #pragma unroll
     for (int r = 0; r < 4; r++) DOUT(4 * r + i) = (fp[r] - fm[r]) / (2 * e);
   };
   if (PART == 0) {  // x, y (one RK4, dyn_jac_xy) and speed columns
-    const UPre q0 = upre<false>(u[1], bad);
-    dyn_jac_xy<false>(s, u[0], q0, P.dT, e, out, stride, bad);
+    const UPre q0 = upre(u[1]);
+    dyn_jac_xy(s, u[0], q0, P.dT, e, out, stride);
     state_col(2, q0);
   } else if (PART == 1) {  // heading column and the ax column of B
-    const UPre q0 = upre<false>(u[1], bad);
+    const UPre q0 = upre(u[1]);
     state_col(3, q0);
     double fp[4], fm[4];
-    rk4<false>(s, u[0] + e, q0, P.dT, fp, bad);
-    rk4<false>(s, u[0] - e, q0, P.dT, fm, bad);
+    rk4(s, u[0] + e, q0, P.dT, fp);
+    rk4(s, u[0] - e, q0, P.dT, fm);
 #pragma unroll
     for (int r = 0; r < 4; r++) DOUT(16 + 2 * r + 0) = (fp[r] - fm[r]) / (2 * e);
   } else if (PART == 2) {  // the δ column of B
     double fp[4], fm[4];
-    const UPre qp = upre<false>(u[1] + e, bad), qm = upre<false>(u[1] - e, bad);
-    rk4<false>(s, u[0], qp, P.dT, fp, bad);
-    rk4<false>(s, u[0], qm, P.dT, fm, bad);
+    const UPre qp = upre(u[1] + e), qm = upre(u[1] - e);
+    rk4(s, u[0], qp, P.dT, fp);
+    rk4(s, u[0], qm, P.dT, fm);
 #pragma unroll
     for (int r = 0; r < 4; r++) DOUT(16 + 2 * r + 1) = (fp[r] - fm[r]) / (2 * e);
   } else {
-    knot_cost_derivs<false>(P, s, u, out, stride, bad);
+    knot_cost_derivs(P, s, u, out, stride);
   }
 #undef DOUT
 }
@@ -772,10 +668,7 @@ __device__ __forceinline__ void backward_sweep_quad(const IlqrDev& P, int b, boo
   }
 }
 
-#ifndef ILQR_LOADER_DEPTH
-#define ILQR_LOADER_DEPTH 2
-#endif
-constexpr int kLoaderDepth = ILQR_LOADER_DEPTH;  // knots of records in flight in the loader wave
+constexpr int kLoaderDepth = 2;  // knots of records in flight in the loader wave (measured below)
 
 // The loader wave of a quad-sweep block: knot j's records of the block's IPB instances into LDS
 // buffer t&1 ([ND][IPB]) before barrier t; lane l loads components l/IPB, l/IPB + 64/IPB, ... of
@@ -859,27 +752,16 @@ __global__ __launch_bounds__(128) void ilqr_backward_quad_kernel(IlqrDev P, int 
 // the same operations on the same operands as the two-kernel path, so the gains are the same bits; the
 // 464 B per knot record round trip through HBM and the separate derivative launch are gone, and the
 // derivative work runs on the SIMDs the sweep leaves idle (one compute wave per CU).
-#ifndef ILQR_FUSED_DW
-#define ILQR_FUSED_DW 7
-#endif
 // derivative waves per block: at most 7, so no SIMD holds more than two of the block's waves and the
 // sweep keeps the ~230 VGPRs it needs (9 waves cap every wave at 168: the sweep spilled 240 B per lane).
 // One wave per part (4) could not keep up with the sweep: 0.292 ms per backward pass vs 0.264 ms for
 // the two-kernel path (profiles/r04_ilqr_fused_ab.txt).
-constexpr int kFusedDW = ILQR_FUSED_DW;
-#ifndef ILQR_FUSED_PARTS
-#define ILQR_FUSED_PARTS 2
-#endif
-// wave-uniform parts per record: 2 = the Jacobians (9 RK4 sharing stage sincos) / the cost
-// derivatives; 4 = knot_derivs_part (three Jacobian parts without the sharing + the costs)
-constexpr int kFusedParts = ILQR_FUSED_PARTS;
-static_assert(kFusedParts == 2 || kFusedParts == 4, "2 or 4 parts");
-static_assert(kFusedDW >= 1 && kFusedDW <= 7, "at most two waves per SIMD");
+constexpr int kFusedDW = 7;
+// wave-uniform parts per record: the Jacobians (9 RK4 sharing stage sincos, knot_dyn_derivs) / the cost
+// derivatives (knot_cost_derivs)
+constexpr int kFusedParts = 2;
 constexpr int kFusedGK = 4;  // knots per group: 4 knots x 16 instances = 64 lanes
-#ifndef ILQR_FUSED_RG
-#define ILQR_FUSED_RG 4
-#endif
-constexpr int kFusedRG = ILQR_FUSED_RG;  // ring slots (groups); LDS = RG x GK x ND x 16 x 8 B
+constexpr int kFusedRG = 4;  // ring slots (groups); LDS = RG x GK x ND x 16 x 8 B
 constexpr size_t kFusedLds = sizeof(double) * kFusedRG * kFusedGK * ND * kQuadIPB;
 
 __device__ __forceinline__ int lds_ld(const int* p) {
@@ -955,16 +837,8 @@ __global__ __launch_bounds__(64 * (1 + kFusedDW)) void ilqr_backward_fused_kerne
       const double sv[4] = {xs[0], xs[1], xs[2], xs[3]};
       const double uv[2] = {us[0], us[1]};
       double* out = ring + ((size_t)slot * kFusedGK + kk) * ND * kQuadIPB + ci;
-      if (kFusedParts == 2) {  // the Jacobians (shared stage sincos, knot_dyn_derivs) / the cost derivatives
-        int bad = 0;
-        if (part == 0) knot_dyn_derivs<false>(P, sv, uv, out, kQuadIPB, bad);
-        else knot_cost_derivs<false>(P, sv, uv, out, kQuadIPB, bad);
-      } else {
-        if (part == 0) knot_derivs_part<0>(P, sv, uv, out, kQuadIPB);
-        else if (part == 1) knot_derivs_part<1>(P, sv, uv, out, kQuadIPB);
-        else if (part == 2) knot_derivs_part<2>(P, sv, uv, out, kQuadIPB);
-        else knot_derivs_part<3>(P, sv, uv, out, kQuadIPB);
-      }
+      if (part == 0) knot_dyn_derivs(P, sv, uv, out, kQuadIPB);
+      else knot_cost_derivs(P, sv, uv, out, kQuadIPB);
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");  // this wave's record writes retired
       if (lane == 0) __hip_atomic_fetch_add(ready + slot, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
@@ -987,9 +861,8 @@ __global__ __launch_bounds__(64 * (1 + kFusedDW)) void ilqr_backward_fused_kerne
 // state stays in registers (Xn is only written), the next knot's reference state, gains and
 // nominal control are loaded one knot ahead, and TotalCost (Cost.jl:1-8) is accumulated in
 // the loop in the reference's order (J = J + stage_i, then + terminal).
-template <bool F, bool SC = F>
 __device__ double forward_trial(const IlqrDev& P, const double* X, const double* U, const double* k,
-                                const double* Kg, double alpha, double* Xn, double* Un, bool wr, int& bad) {
+                                const double* Kg, double alpha, double* Xn, double* Un, bool wr) {
   const int N = P.N;
   double x[4] = {X[0], X[1], X[2], X[3]};
   if (wr)
@@ -1021,10 +894,10 @@ __device__ double forward_trial(const IlqrDev& P, const double* X, const double*
       Un[2 * i] = u[0];
       Un[2 * i + 1] = u[1];
     }
-    J = J + stage<F>(P.variant, x, u, bad);
-    const UPre q = upre<F>(u[1], bad);
+    J = J + stage(P.variant, x, u);
+    const UPre q = upre(u[1]);
     double xn[4];
-    rk4_ilp<SC>(x, u[0], q, P.dT, xn, bad);
+    rk4_ilp(x, u[0], q, P.dT, xn);
 #pragma unroll
     for (int r = 0; r < 4; r++) {
       x[r] = xn[r];
@@ -1043,9 +916,6 @@ __device__ double forward_trial(const IlqrDev& P, const double* X, const double*
   return J + terminal(P.variant, x);
 }
 
-#ifndef ILQR_FWD_NOSTORE
-#define ILQR_FWD_NOSTORE 0  // timing probe only: the forward kernel's trajectory stores off
-#endif
 // Broadcast lane j of each quad to the quad (DPP quad_perm [j,j,j,j]).
 template <int J>
 __device__ __forceinline__ double quad_bcast(double v) {
@@ -1066,7 +936,6 @@ __device__ double forward_trial_quad(const IlqrDev& P, const double* X, const do
                                      const double* Kg, double alpha, double* Xn, double* Un, bool wr, int sub) {
   const int N = P.N;
   const double la = 1.56, lb = 1.64, dT = P.dT;
-  int bad = 0;
   double x[4] = {X[0], X[1], X[2], X[3]};
   // the trajectory is written a knot group at a time: every lane holds the whole state, lane sub
   // keeps knot j of X and knot i of U with j, i = sub (mod 4), and after each 4th knot the quad
@@ -1114,7 +983,7 @@ __device__ double forward_trial_quad(const IlqrDev& P, const double* X, const do
       J = J + stage_pre(P.variant, x, u[0], u[1], sd, sa);
     }
     // RK4Integration with the stage sincos spread over the quad
-    const UPre q = upre<false>(u[1], bad);
+    const UPre q = upre(u[1]);
     const double ax = u[0];
     const double k1_3 = x[2] * q.cb * q.tdl / (la + lb);
     const double x2_2 = x[2] + dT / 2 * ax, x2_3 = x[3] + dT / 2 * k1_3;
@@ -1184,14 +1053,10 @@ __device__ __forceinline__ double pair_bcast(double v) {
 // (round 0 at full activity).  Same operations on the same operands: bit-identical.
 // The trajectory goes out in 4-knot groups: knot j of a group is held by lane (j & 3) >> 1, slot
 // j & 1, and each lane writes its two consecutive knots (64 B of X, 32 B of U).
-#ifndef ILQR_PAIR_PRIO
-#define ILQR_PAIR_PRIO 0  // (A/B) quarter priority levels in the pair trial
-#endif
 __device__ double forward_trial_pair(const IlqrDev& P, const double* X, const double* U, const double* k,
                                      const double* Kg, double alpha, double* Xn, double* Un, bool wr, int sub) {
   const int N = P.N;
   const double la = 1.56, lb = 1.64, dT = P.dT;
-  int bad = 0;
   double x[4] = {X[0], X[1], X[2], X[3]};
   double sx[2][4], su[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
 #pragma unroll
@@ -1204,17 +1069,7 @@ __device__ double forward_trial_pair(const IlqrDev& P, const double* X, const do
   for (int r = 0; r < 8; r++) Kr[r] = Kg[r];
   kr[0] = k[0]; kr[1] = k[1];
   ur[0] = U[0]; ur[1] = U[1];
-#if ILQR_PAIR_PRIO
-  // (A/B) self-balancing issue priority over the trial's knots (a wave drops one level per quarter)
-  const int q1 = (N - 1) / 4, q2 = (N - 1) / 2, q3 = 3 * (N - 1) / 4;
-  __builtin_amdgcn_s_setprio(3);
-#endif
   for (int i = 0; i < N - 1; i++) {
-#if ILQR_PAIR_PRIO
-    if (i == q1) __builtin_amdgcn_s_setprio(2);
-    else if (i == q2) __builtin_amdgcn_s_setprio(1);
-    else if (i == q3) __builtin_amdgcn_s_setprio(0);
-#endif
     const int in = i + 2 < N ? i + 1 : i;  // knot i+1 (clamped)
     double nxr[4], nK[8], nk[2], nu[2];
 #pragma unroll
@@ -1247,7 +1102,7 @@ __device__ double forward_trial_pair(const IlqrDev& P, const double* X, const do
       const double sa = mag * (a1 + a2), sd = mag * (d1 + d2);
       J = J + stage_pre(P.variant, x, u[0], u[1], sd, sa);
     }
-    const UPre q = upre<false>(u[1], bad);
+    const UPre q = upre(u[1]);
     const double ax = u[0];
     const double k1_3 = x[2] * q.cb * q.tdl / (la + lb);
     const double x2_2 = x[2] + dT / 2 * ax, x2_3 = x[3] + dT / 2 * k1_3;
@@ -1319,10 +1174,14 @@ __global__ __launch_bounds__(64) void ilqr_forward_quad_kernel(IlqrDev P, int B,
   const size_t b = live ? b0 : B - 1;  // all lanes active (DPP quads); tail quads store nothing
   const size_t N = P.N;
   const double J = forward_trial_quad(P, X + b * N * 4, U + b * N * 2, k + b * (N - 1) * 2, Kg + b * (N - 1) * 8,
-                                      alpha[b], Xn + b * N * 4, Un + b * N * 2, live && !ILQR_FWD_NOSTORE, sub);
+                                      alpha[b], Xn + b * N * 4, Un + b * N * 2, live, sub);
   if (live && sub == 0) Jn[b] = J;
 }
 
+// The trial on one lane per instance as a kernel of its own.  No entry point launches it (mp_ilqr_forward runs
+// the quad kernel above); it stays because it is forward_trial's only caller whose write flag is a run-time
+// value: without it the compiler folds wr = true into forward_trial and schedules the loads of
+// ilqr_search_kernel<4> and <1> differently (profiles/switch_retire_isa.txt).
 __global__ __launch_bounds__(64) void ilqr_forward_kernel(IlqrDev P, int B, const double* X, const double* U,
                                                           const double* k, const double* Kg, const double* alpha,
                                                           double* Xn, double* Un, double* Jn) {
@@ -1330,14 +1189,8 @@ __global__ __launch_bounds__(64) void ilqr_forward_kernel(IlqrDev P, int B, cons
   const bool live = b0 < B;
   const size_t b = live ? b0 : B - 1;  // all lanes active (ballot-based libm); tail lanes store nothing
   const size_t N = P.N;
-  int bad = 0;
-  double J = forward_trial<kFastFwd, kFastSC>(P, X + b * N * 4, U + b * N * 2, k + b * (N - 1) * 2,
-                                             Kg + b * (N - 1) * 8, alpha[b], Xn + b * N * 4, Un + b * N * 2, live, bad);
-  if ((kFastFwd || kFastSC) && kRedo && __any(bad)) {  // redo the wave's trials with the exact libm
-    int d = 0;
-    J = forward_trial<false>(P, X + b * N * 4, U + b * N * 2, k + b * (N - 1) * 2, Kg + b * (N - 1) * 8, alpha[b],
-                             Xn + b * N * 4, Un + b * N * 2, live, d);
-  }
+  const double J = forward_trial(P, X + b * N * 4, U + b * N * 2, k + b * (N - 1) * 2, Kg + b * (N - 1) * 8, alpha[b],
+                                 Xn + b * N * 4, Un + b * N * 2, live);
   if (live) Jn[b] = J;
 }
 
@@ -1447,8 +1300,7 @@ __device__ __forceinline__ void search_round0(const IlqrDev& P, int B, double* X
       } else if (L == 2) {
         jt = forward_trial_pair(P, Xb, Ub, kb, Kb, ldexp(1.0, -m), Xg, Ug, true, sub);
       } else {
-        int d = 0;
-        jt = forward_trial<false>(P, Xb, Ub, kb, Kb, ldexp(1.0, -m), Xg, Ug, true, d);
+        jt = forward_trial(P, Xb, Ub, kb, Kb, ldexp(1.0, -m), Xg, Ug, true);
       }
     }
     const bool stop = mine && (!(jt >= J) || m == P.ls_cap || m == ms);
@@ -1534,10 +1386,8 @@ __device__ __forceinline__ void search_rest(const IlqrDev& P, int B, const doubl
                             ldexp(1.0, -m), Xs2 + ((size_t)b * T2 + t) * N * 4, Us2 + ((size_t)b * T2 + t) * N * 2,
                             true, sub);
   } else {
-    int d = 0;
-    jt = forward_trial<false>(P, X + b * N * 4, U + b * N * 2, k + b * (N - 1) * 2, Kg + b * (N - 1) * 8,
-                              ldexp(1.0, -m), Xs2 + ((size_t)b * T2 + t) * N * 4, Us2 + ((size_t)b * T2 + t) * N * 2,
-                              true, d);
+    jt = forward_trial(P, X + b * N * 4, U + b * N * 2, k + b * (N - 1) * 2, Kg + b * (N - 1) * 8,
+                       ldexp(1.0, -m), Xs2 + ((size_t)b * T2 + t) * N * 4, Us2 + ((size_t)b * T2 + t) * N * 2, true);
   }
   if (sub != 0) return;
   Jt[(size_t)b * T2 + t] = jt;
@@ -1557,19 +1407,10 @@ __global__ __launch_bounds__(64) void ilqr_search_rest_kernel(IlqrDev P, int B, 
 // iteration's round 0 left pending (blocks n0.., instance-major within each 16-trial column), so
 // the rest pass's latency hides under round 0 instead of following it.  An instance's own sequence
 // of operations is unchanged (its next backward pass simply comes one launch later).
-// (A/B) ILQR_PIPE_WPE: waves per SIMD the pipelined search kernel is compiled for (0: the compiler's choice,
-// 244 VGPRs = 2 waves per SIMD -- exactly the 2,048 round-0 waves of a full-activity launch, so the rest-pass
-// waves of the same launch wait for round-0 waves to retire instead of running beside them)
-#ifndef ILQR_PIPE_WPE
-#define ILQR_PIPE_WPE 0
-#endif
-#if ILQR_PIPE_WPE
-#define ILQR_PIPE_ATTR __attribute__((amdgpu_waves_per_eu(ILQR_PIPE_WPE)))
-#else
-#define ILQR_PIPE_ATTR
-#endif
+// (Waves per SIMD are the compiler's choice: 244 VGPRs = 2 per SIMD -- exactly the 2,048 round-0 waves of a
+// full-activity launch, so the rest-pass waves of the same launch wait for round-0 waves to retire.)
 template <int G, int L, int L0 = L>
-__global__ __launch_bounds__(64) ILQR_PIPE_ATTR void ilqr_search_pipe_kernel(IlqrDev P, int B, double* X, double* U, const double* k,
+__global__ __launch_bounds__(64) void ilqr_search_pipe_kernel(IlqrDev P, int B, double* X, double* U, const double* k,
                                                               const double* Kg, double* Xs, double* Us, double* Jcur,
                                                               int* active, int* iters, int* flags, int* n_active,
                                                               int* pend_new, int* mstar_new, int* npend_new,
@@ -1619,9 +1460,8 @@ __global__ __launch_bounds__(64) void ilqr_search_finish_kernel(IlqrDev P, int B
 }
 
 // Initial guess roll out (ILQR.jl:31-37) with TotalCost accumulated in order.
-template <bool F, bool SC = F>
 __device__ __forceinline__ double rollout_one(const IlqrDev& P, const double* x0, const double* Ub, double* Xb,
-                                              bool live, int& bad) {
+                                              bool live) {
   const size_t N = P.N;
   double x[4] = {x0[0], x0[1], x0[2], x0[3]};
   if (live)
@@ -1630,10 +1470,10 @@ __device__ __forceinline__ double rollout_one(const IlqrDev& P, const double* x0
   double Jb = 0.0;
   for (size_t i = 0; i + 1 < N; i++) {
     const double u[2] = {Ub[2 * i], Ub[2 * i + 1]};
-    Jb = Jb + stage<F>(P.variant, x, u, bad);
-    const UPre q = upre<F>(u[1], bad);
+    Jb = Jb + stage(P.variant, x, u);
+    const UPre q = upre(u[1]);
     double xn[4];
-    rk4_ilp<SC>(x, u[0], q, P.dT, xn, bad);
+    rk4_ilp(x, u[0], q, P.dT, xn);
 #pragma unroll
     for (int r = 0; r < 4; r++) {
       x[r] = xn[r];
@@ -1649,12 +1489,7 @@ __global__ __launch_bounds__(64) void ilqr_rollout_kernel(IlqrDev P, int B, cons
   const bool live = b0 < B;
   const size_t b = live ? b0 : B - 1;  // all lanes active (ballot-based libm)
   const size_t N = P.N;
-  int bad = 0;
-  double Jb = rollout_one<kFastFwd, kFastSC>(P, x0 + 4 * b, U + b * N * 2, X + b * N * 4, live, bad);
-  if ((kFastFwd || kFastSC) && kRedo && __any(bad)) {
-    int d = 0;
-    Jb = rollout_one<false>(P, x0 + 4 * b, U + b * N * 2, X + b * N * 4, live, d);
-  }
+  const double Jb = rollout_one(P, x0 + 4 * b, U + b * N * 2, X + b * N * 4, live);
   if (live) J[b] = Jb;
 }
 
@@ -1805,12 +1640,8 @@ int mp_ilqr_forward(mp_ctx* ctx, const mp_ilqr_params* p, int32_t B, const doubl
   double* dJ = mp_alloc_out(ctx, WS_IO7, Jnew, (size_t)B, &st);
   if (st) return st;
   mp_time_begin(ctx);
-  if (kFwdQuad)
-    hipLaunchKernelGGL(ilqr_forward_quad_kernel, dim3((B + 15) / 16), dim3(64), 0, ctx->stream, D, B, dX, dU, dk, dK,
-                       da, dXn, dUn, dJ);
-  else
-    hipLaunchKernelGGL(ilqr_forward_kernel, dim3((B + 63) / 64), dim3(64), 0, ctx->stream, D, B, dX, dU, dk, dK, da,
-                       dXn, dUn, dJ);
+  hipLaunchKernelGGL(ilqr_forward_quad_kernel, dim3((B + 15) / 16), dim3(64), 0, ctx->stream, D, B, dX, dU, dk, dK,
+                     da, dXn, dUn, dJ);
   MP_HIP(ctx, hipGetLastError());
   mp_time_end(ctx);
   if ((st = mp_download(ctx, Xnew, (const double*)dXn, 4 * N * B))) return st;
@@ -1839,12 +1670,8 @@ int mp_ilqr_forward_dev(mp_ctx* ctx, const mp_ilqr_params* p, int32_t B, const d
   if (st) return st;
   MP_CHECK(ctx, X && U && k && Kg && alpha && Xnew && Unew && Jnew, "required pointer is NULL");
   mp_time_begin(ctx);
-  if (kFwdQuad)
-    hipLaunchKernelGGL(ilqr_forward_quad_kernel, dim3((B + 15) / 16), dim3(64), 0, ctx->stream, D, B, X, U, k, Kg,
-                       alpha, Xnew, Unew, Jnew);
-  else
-    hipLaunchKernelGGL(ilqr_forward_kernel, dim3((B + 63) / 64), dim3(64), 0, ctx->stream, D, B, X, U, k, Kg, alpha,
-                       Xnew, Unew, Jnew);
+  hipLaunchKernelGGL(ilqr_forward_quad_kernel, dim3((B + 15) / 16), dim3(64), 0, ctx->stream, D, B, X, U, k, Kg,
+                     alpha, Xnew, Unew, Jnew);
   MP_HIP(ctx, hipGetLastError());
   mp_time_end(ctx);
   return MP_OK;
@@ -1976,10 +1803,9 @@ static int ilqr_solve(mp_ctx* ctx, const mp_ilqr_params* p, int32_t B, double* X
     return MP_OK;
   };
   // pipelined two-pass search (ilqr_search_pipe_kernel): launch q marks pend[q & 1] and runs the rest
-  // pass of pend[(q - 1) & 1]; pend[1] starts empty
-  const bool pipe = rest && kPipe;
+  // pass of pend[(q - 1) & 1], so each rest pass overlaps the next iteration's round 0; pend[1] starts empty
   int q2 = 0;  // two-pass launches so far
-  if (pipe) {  // pend[2][B] = 0, winm[2][B] = 0x7f7f7f7f; afterwards the finish kernels reset what they use
+  if (rest) {  // pend[2][B] = 0, winm[2][B] = 0x7f7f7f7f; afterwards the finish kernels reset what they use
     MP_HIP(ctx, hipMemsetAsync(dpw, 0, sizeof(int) * 2 * B, ctx->stream));
     MP_HIP(ctx, hipMemsetAsync(dpw + 2 * B, 0x7f, sizeof(int) * 2 * B, ctx->stream));
   }
@@ -2025,10 +1851,10 @@ static int ilqr_solve(mp_ctx* ctx, const mp_ilqr_params* p, int32_t B, double* X
       continue;
     }
     // G = 16: a lane quad per trial (4 waves per SIMD at B = 4096); the narrower fallbacks one lane
-    const int l0 = pipe && n_act >= kPairMin ? kRound0L : kSearchL;
+    const int l0 = rest && n_act >= kPairMin ? kRound0L : kSearchL;
     const int ipw = G == kSearchG ? 64 / (kSearchG * l0) : 64 / G;
     const dim3 gs((unsigned)((B + ipw - 1) / ipw));
-    if (pipe) {
+    if (rest) {
       const int cur = q2 & 1, old = cur ^ 1;
       q2++;
       int *pend_n = dpw + cur * B, *pend_o = dpw + old * B;
@@ -2051,30 +1877,17 @@ static int ilqr_solve(mp_ctx* ctx, const mp_ilqr_params* p, int32_t B, double* X
       if (stop) break;
       continue;
     }
-    if (rest) {
-      MP_HIP(ctx, hipMemsetAsync(dpw, 0, sizeof(int) * B, ctx->stream));             // pending
-      MP_HIP(ctx, hipMemsetAsync(dpw + B, 0x7f, sizeof(int) * B, ctx->stream));      // winm = 0x7f7f7f7f
-    }
+    // no rest-pass slots: the G-wide kernel runs its rounds to the end
     if (G == kSearchG)
       hipLaunchKernelGGL((ilqr_search_kernel<kSearchG, kSearchL>), gs, b1, 0, ctx->stream, D, B, dX, dU, dk, dK, dXn, dUn, dJ, dact,
-                         dit, dfl, dn, rest ? 1 : 0, dpw, dpw ? dpw + 2 * B : nullptr);
+                         dit, dfl, dn, 0, nullptr, nullptr);
     else if (G == 4)
       hipLaunchKernelGGL(ilqr_search_kernel<4>, gs, b1, 0, ctx->stream, D, B, dX, dU, dk, dK, dXn, dUn, dJ, dact, dit, dfl, dn,
-                         0, dpw, nullptr);
+                         0, nullptr, nullptr);
     else
       hipLaunchKernelGGL(ilqr_search_kernel<1>, gs, b1, 0, ctx->stream, D, B, dX, dU, dk, dK, dXn, dUn, dJ, dact, dit, dfl, dn,
-                         0, dpw, nullptr);
+                         0, nullptr, nullptr);
     MP_HIP(ctx, hipGetLastError());
-    if (rest) {
-      hipLaunchKernelGGL((ilqr_search_rest_kernel<kSearchG, kSearchL>), dim3((unsigned)B, (unsigned)((T2 + 64 / kSearchL - 1) /
-                         (64 / kSearchL))), b1, 0, ctx->stream, D, B, dX, dU, dk, dK, dJ, dpw, dpw + 2 * B, dXs2, dUs2, dJt, dpw + B, kSearchG,
-                         T2);
-      MP_HIP(ctx, hipGetLastError());
-      hipLaunchKernelGGL(ilqr_search_finish_kernel<kSearchG>, dim3((unsigned)B), b1, 0, ctx->stream, D, B, dX, dU, dpw, dpw + 2 * B,
-                         dXs2, dUs2, dJt, dpw + B, dJ, dact, dit, dfl, dn, kSearchG, T2, 0, zn);
-      MP_HIP(ctx, hipGetLastError());
-      w_zeroed = zn != nullptr;
-    }
     mp_time_end(ctx);
     bool stop;
     if ((st = poll(outer, &stop))) return st;

@@ -6,7 +6,7 @@
 //            dynamics and all step costs fused; per-rollout cost/flag and the
 //            control list go to HBM (the TrajectoryCollection contract);
 //            the two waves sharing a SIMD pace each other by issue priority
-//            (MPPI_PRIO 3).  Then the block's online-softmax partial (ρ_b, η_b,
+//            (sibling-paced, see ctrl()).  Then the block's online-softmax partial (ρ_b, η_b,
 //            Σ e·u; the latter per wave over its own rollouts, from registers
 //            prefetched when the wave ends) is published with agent-coherent
 //            stores (sc1), every thread's stores acknowledged, then an arrival
@@ -31,9 +31,6 @@ namespace {
 
 constexpr int NT = 256;     // threads per block (4 waves)
 constexpr int RPB = NT / 2; // rollouts per block
-#ifndef MPPI_PRIO
-#define MPPI_PRIO 3  // issue-priority scheme of the rollout loop (see ctrl()); 0 = quarters (round 2)
-#endif
 // Dynamic LDS budgets per block (160 KiB per CU on gfx950).  The plan kernel's static LDS is at most
 // 13,096 B (BT 512, LPR 2: sh_q 8 KiB, sh_e 2 KiB, the atan rows and bounds 2,704 B, the rest < 200 B), so one block
 // fits beside 146 KiB, and at most 7,976 B at BT 256, so two blocks fit beside 70 KiB each.
@@ -96,10 +93,6 @@ struct PlanArgs {
   int fin_stride;                   // doubles per scene record
   const int* live;                  // closed loop: scenes with live[s] == 0 are skipped (null: all run)
 };
-
-#ifndef MPPI_NT_CTRL
-#define MPPI_NT_CTRL 0
-#endif
 
 // The occupancy grid's LDS image (staged 16 bytes per lane) starts at the first 16-byte line of its region plus
 // the scene's offset within a line of the caller's buffer: up to 15 + 15 bytes into the region.
@@ -187,15 +180,11 @@ template <class T>
 __device__ __forceinline__ T ld_ag(const T* p) {
   return __hip_atomic_load(const_cast<T*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-// The arrival of a block's records at the scene's last block.  0 (default): each thread's records
-// acknowledged (vmcnt), then an agent-scope release fence before the relaxed ticket and an acquire fence in
-// the last block -- ordered within the HIP/HSA memory model.  1 (A/B): the records are agent-coherent stores
-// and the ticket relaxed, ordered by the per-thread vmcnt wait alone (sound on gfx94x/95x hardware, but
-// outside the language model); round 4 measured no gain from it (profiles/r04w_mppi_coherent_ha_scan_ab.txt),
-// so the fenced form is the default.
-#ifndef MPPI_COHERENT_PARTS
-#define MPPI_COHERENT_PARTS 0
-#endif
+// The arrival of a block's records at the scene's last block: each thread's records acknowledged (vmcnt),
+// then an agent-scope release fence before the relaxed ticket and an acquire fence in the last block --
+// ordered within the HIP/HSA memory model.  (Relying on the agent-coherent stores, the relaxed ticket and the
+// per-thread vmcnt wait alone is sound on gfx94x/95x hardware but outside the language model, and round 4
+// measured no gain from it, profiles/r04w_mppi_coherent_ha_scan_ab.txt: the fenced form stays)
 
 // BT threads per block (4 or 8 waves); LPR lanes per rollout: 2 = lane pair (dyn_pair, the
 // two tire chains on the two lanes), 1 = one rollout per lane (dyn_lane) when the launch has a
@@ -297,7 +286,6 @@ __global__ __launch_bounds__(BT) void mppi_plan_kernel(MppiDev P, PlanArgs A) {
   // = 1, 2, 3, are j = ceil(qH / 4): one j per q, since [qH, qH + 4) holds one multiple of 4
   const int pq1 = (H + 3) >> 2, pq2 = (2 * H + 3) >> 2, pq3 = (3 * H + 3) >> 2;
 
-#if MPPI_PRIO == 3
   // Sibling-paced issue priority: each wave publishes its step in LDS and finds the other wave of the
   // block on its SIMD (HW_ID.SIMD_ID); per step it drops below the sibling when ahead of it and rises
   // above it when behind, so the pair ends together instead of one wave finishing the horizon alone.
@@ -319,7 +307,6 @@ __global__ __launch_bounds__(BT) void mppi_plan_kernel(MppiDev P, PlanArgs A) {
     sib = __builtin_amdgcn_readfirstlane(sib);
   }
   int sib_j = 0;
-#endif
   // ---------------- phase 1: the rollout of this lane pair
   int feas;
   double c;
@@ -353,17 +340,9 @@ __global__ __launch_bounds__(BT) void mppi_plan_kernel(MppiDev P, PlanArgs A) {
       }
       const double z[2] = {zj.x, zj.y};
       sample_ctrl(P, z, unom + 2 * j, u);
-      // Self-balancing issue priority: a wave's priority drops by one per quarter of the
-      // horizon it has completed, so the waves sharing a SIMD (oldest-first arbitration
-      // otherwise lets one run ahead and leaves the other to finish alone) end together.
-#if MPPI_PRIO == 0
-      if ((4 * j) % H < 4 && j > 0) {
-        const int q = (4 * j) / H;
-        if (q == 1) __builtin_amdgcn_s_setprio(2);
-        else if (q == 2) __builtin_amdgcn_s_setprio(1);
-        else if (q == 3) __builtin_amdgcn_s_setprio(0);
-      }
-#elif MPPI_PRIO == 3
+      // Self-balancing issue priority, so that the waves sharing a SIMD (oldest-first arbitration otherwise
+      // lets one run ahead and leaves the other to finish alone) end together: paced by the sibling's step,
+      // or, with no sibling, dropping by one per quarter of the horizon completed.
       if (sib >= 0) {
         // sib_j was read one step ago (its LDS latency hidden behind the step)
         const int o = __builtin_amdgcn_readfirstlane(sib_j);
@@ -390,17 +369,6 @@ __global__ __launch_bounds__(BT) void mppi_plan_kernel(MppiDev P, PlanArgs A) {
         else if (q == 2) __builtin_amdgcn_s_setprio(1);
         else if (q == 3) __builtin_amdgcn_s_setprio(0);
       }
-#else
-      // (A/B) levels crowded towards the end of the horizon, where a lag turns into lone-wave time:
-      // 1: H/2, 3H/4, 7H/8;  2: H-12, H-6, H-3
-      if (j > 0) {
-        const int t1 = MPPI_PRIO == 1 ? H / 2 : H - 12, t2 = MPPI_PRIO == 1 ? 3 * H / 4 : H - 6,
-                  t3 = MPPI_PRIO == 1 ? 7 * H / 8 : H - 3;
-        if (j == t1) __builtin_amdgcn_s_setprio(2);
-        else if (j == t2) __builtin_amdgcn_s_setprio(1);
-        else if (j == t3) __builtin_amdgcn_s_setprio(0);
-      }
-#endif
     };
     auto store = [&](int j, const double* u) {
       if (LEAN) {
@@ -409,13 +377,7 @@ __global__ __launch_bounds__(BT) void mppi_plan_kernel(MppiDev P, PlanArgs A) {
         ctrl_u += ctrl_row;
       } else if (LPR == 2) {
         if (ush) ush[pair * ustr + 2 * j + side] = u[side];
-        if (ctrl_g) {
-#if MPPI_NT_CTRL
-          __builtin_nontemporal_store(u[side], ctrl_g + (size_t)j * K * 2);
-#else
-          ctrl_g[(size_t)j * K * 2] = u[side];
-#endif
-        }
+        if (ctrl_g) ctrl_g[(size_t)j * K * 2] = u[side];
       } else {
         if (ush) {
           ush[pair * ustr + 2 * j] = u[0];
@@ -550,15 +512,11 @@ __global__ __launch_bounds__(BT) void mppi_plan_kernel(MppiDev P, PlanArgs A) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (tid == 0) {
-    if (!MPPI_COHERENT_PARTS) {
-      __threadfence();  // agent-scope release: write back this XCD's L2
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
+    __threadfence();  // agent-scope release: write back this XCD's L2
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     const unsigned t = __hip_atomic_fetch_add(A.tickets + s, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     sh_last = (t == (unsigned)(A.nb - 1));
-    // the last block reads the partials agent-coherently while it stages them in LDS; without the
-    // stage (too little LDS) it reads them with plain loads, after an acquire
-    if (sh_last && (!MPPI_COHERENT_PARTS || A.lds_part < 0)) {
+    if (sh_last) {
       __threadfence();  // agent-scope acquire: invalidate this CU's L1
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }

@@ -414,21 +414,14 @@ __device__ __forceinline__ mp_gchar* uni_addr(unsigned long long& base, unsigned
 // The even lane of the pair stores x[0..3], the odd lane x[4..6] (LPR 1: the lane all 7).
 // TrajectoryCollection states are written once and read only by the caller: non-temporal stores
 // (streaming, no L2 residency) -- 1.5-2 % off the 8-scene plan kernel (profiles/r03nt2_mppi_nt_ab.txt).
-#ifndef MPPI_NT_STATE
-#define MPPI_NT_STATE 1
-#endif
-__device__ __forceinline__ void st_state(double* a, double v) {
-  if (MPPI_NT_STATE) __builtin_nontemporal_store(v, a);
-  else *a = v;
-}
+__device__ __forceinline__ void st_state(double* a, double v) { __builtin_nontemporal_store(v, a); }
 template <int LPR = 2>
 __device__ __forceinline__ void store_state(TrajUni& T, int, const double* x, int) {
   static_assert(LPR == 1, "uniform-base stores: one rollout per lane");
 #pragma unroll
   for (int i = 0; i < 7; i++) {
     auto* q = reinterpret_cast<__attribute__((address_space(1))) double*>(uni_addr(T.base, T.off));
-    if (MPPI_NT_STATE) __builtin_nontemporal_store(x[i], q);
-    else *q = x[i];
+    __builtin_nontemporal_store(x[i], q);
     T.base += T.cs;  // after the seven rows: the next step's
   }
 }

@@ -316,7 +316,7 @@ def test_rare_partial_waves(ctx, B, slots):
 
 
 def test_rare_fused_backward_path(ctx):
-    """B = 2064 > ILQR_DERIV4_MAX: run_backward takes ilqr_backward_fused_kernel.  Rare instances scattered through
+    """B = 2064 > kDeriv4Max: run_backward takes ilqr_backward_fused_kernel.  Rare instances scattered through
     the batch (every 97th slot and the last); the same batch cut to 48 instances takes the deriv4 + quad path, and
     both agree with the oracle, hence with each other."""
     B, N = 2064, 3
