@@ -2,10 +2,11 @@
 // the PathPlanning/Parking_ILQR variant) for gfx950 + C-ABI entry points.
 //
 // Per outer iteration (ILQR.jl:44-88) for the active instances of a batch:
-//   ilqr_deriv_kernel / ilqr_deriv4_kernel   LocallyLinearizeDynamics (12 RK4) and CalculateMatrix
-//                         (130 StageCost evaluations) by finite differences for every (instance,
-//                         knot): one thread per record, or -- launches with few active instances --
-//                         four waves per 64 records, one part of the derivatives each.  Control-only
+//   ilqr_deriv4_kernel    LocallyLinearizeDynamics (12 RK4) and CalculateMatrix (130 StageCost
+//                         evaluations) by finite differences for every (instance, knot): four waves per
+//                         64 records, one part of the derivatives each (with many active instances inside
+//                         ilqr_backward_fused_kernel; ilqr_deriv_kernel, one thread per record, is no
+//                         longer launched).  Control-only
 //                         sub-expressions (tan δ, β, cos β, the sigmoid barriers) are evaluated once
 //                         per distinct perturbed control and reused: the same function of the same
 //                         bits, so every derivative is bit-identical to the scalar restatement.
@@ -20,6 +21,7 @@
 //                         first that would end the sequential loop, so the results are the loop's.
 // The host loops until every instance has met |ΔJ/J| <= tol (or its max_iter).
 #include "../../include/mp_jlmath.h"
+#include "ilqr_plan.hpp"
 #include "runtime.hpp"
 
 namespace {
@@ -380,6 +382,9 @@ __device__ __forceinline__ void knot_cost_derivs(const IlqrDev& P, const double*
 // list (mp_ilqr_solve): the n active instances in compact order; record i (of instance list[i])
 // then sits in column i.  Without a list, all B instances, column b.  n_dev: n read on the device
 // (the grid is sized for nmax >= n by a host that has not waited for the count), else n = nmax.
+// No entry point launches this kernel any more (run_backward: the fused kernel above kDeriv4Max active
+// instances, ilqr_deriv4_kernel up to it).  It stays because removing it changes the bodies of
+// ilqr_deriv4_kernel and ilqr_backward_fused_kernel (profiles/ilqr_host_isa.txt).
 __global__ __launch_bounds__(256) void ilqr_deriv_kernel(IlqrDev P, int B, const double* X, const double* U,
                                                          const int* list, const int* n_dev, int nmax, double* D) {
   ilqr_mirror(P, n_dev);
@@ -855,6 +860,42 @@ __global__ __launch_bounds__(64 * (1 + kFusedDW)) void ilqr_backward_fused_kerne
                                 live ? inst : (n - 1 - col0), q);
 }
 
+// RK4Integration for the quad and pair trials, whose lanes share the stages' sines and cosines: the stage
+// speeds and headings (they never depend on a sine or cosine, see rk4_ilp), then the combine.
+struct Rk4Heads {
+  double k1_3, x2_2, x2_3, k2_3, x3_2, x3_3, k3_3, x4_2, x4_3, k4_3;
+  __device__ __forceinline__ Rk4Heads(const double* x, double ax, const UPre& q, double dT) {
+    const double la = 1.56, lb = 1.64;
+    k1_3 = x[2] * q.cb * q.tdl / (la + lb);
+    x2_2 = x[2] + dT / 2 * ax, x2_3 = x[3] + dT / 2 * k1_3;
+    k2_3 = x2_2 * q.cb * q.tdl / (la + lb);
+    x3_2 = x[2] + dT / 2 * ax, x3_3 = x[3] + dT / 2 * k2_3;
+    k3_3 = x3_2 * q.cb * q.tdl / (la + lb);
+    x4_2 = x[2] + dT * ax, x4_3 = x[3] + dT * k3_3;
+    k4_3 = x4_2 * q.cb * q.tdl / (la + lb);
+  }
+  // sc = {s1, c1, .., s4, c4}: sine and cosine of stage j's heading + β
+  __device__ __forceinline__ void combine(const double* x, double ax, double dT, const double* sc, double* xn) const {
+    const double k1[4] = {x[2] * sc[1], x[2] * sc[0], ax, k1_3};
+    const double k2[4] = {x2_2 * sc[3], x2_2 * sc[2], ax, k2_3};
+    const double k3[4] = {x3_2 * sc[5], x3_2 * sc[4], ax, k3_3};
+    const double k4[4] = {x4_2 * sc[7], x4_2 * sc[6], ax, k4_3};
+#pragma unroll
+    for (int r = 0; r < 4; r++) xn[r] = 1.0 / 6 * (k1[r] + 2 * k2[r] + 2 * k3[r] + k4[r]) * dT + x[r];
+  }
+};
+
+// knot i's reference state, gains and nominal control
+__device__ __forceinline__ void knot_load(const double* X, const double* U, const double* k, const double* Kg, int i,
+                                          double (&xr)[4], double (&Kr)[8], double (&kr)[2], double (&ur)[2]) {
+#pragma unroll
+  for (int r = 0; r < 4; r++) xr[r] = X[4 * i + r];
+#pragma unroll
+  for (int r = 0; r < 8; r++) Kr[r] = Kg[8 * i + r];
+  kr[0] = k[2 * i]; kr[1] = k[2 * i + 1];
+  ur[0] = U[2 * i]; ur[1] = U[2 * i + 1];
+}
+
 // ILQR.jl:72-80: one closed-loop roll out at step size alpha; returns TotalCost.  (Staging the
 // per-knot inputs through LDS as the Riccati sweep does measured no gain here, 371 vs 365 us: the
 // one-knot-ahead prefetch already covers the loads under the knot's ~8k-cycle RK4 chain.)  The rolled
@@ -869,22 +910,12 @@ __device__ double forward_trial(const IlqrDev& P, const double* X, const double*
 #pragma unroll
     for (int r = 0; r < 4; r++) Xn[r] = x[r];
   double xr[4], Kr[8], kr[2], ur[2];
-#pragma unroll
-  for (int r = 0; r < 4; r++) xr[r] = X[r];
-#pragma unroll
-  for (int r = 0; r < 8; r++) Kr[r] = Kg[r];
-  kr[0] = k[0]; kr[1] = k[1];
-  ur[0] = U[0]; ur[1] = U[1];
+  knot_load(X, U, k, Kg, 0, xr, Kr, kr, ur);
   double J = 0.0;
   for (int i = 0; i < N - 1; i++) {
     const int in = i + 2 < N ? i + 1 : i;  // prefetch knot i+1 (clamped)
     double nxr[4], nK[8], nk[2], nu[2];
-#pragma unroll
-    for (int r = 0; r < 4; r++) nxr[r] = X[4 * in + r];
-#pragma unroll
-    for (int r = 0; r < 8; r++) nK[r] = Kg[8 * in + r];
-    nk[0] = k[2 * in]; nk[1] = k[2 * in + 1];
-    nu[0] = U[2 * in]; nu[1] = U[2 * in + 1];
+    knot_load(X, U, k, Kg, in, nxr, nK, nk, nu);
     double dx[4], u[2];
 #pragma unroll
     for (int r = 0; r < 4; r++) dx[r] = x[r] - xr[r];
@@ -935,7 +966,7 @@ __device__ __forceinline__ double quad_bcast(double v) {
 __device__ double forward_trial_quad(const IlqrDev& P, const double* X, const double* U, const double* k,
                                      const double* Kg, double alpha, double* Xn, double* Un, bool wr, int sub) {
   const int N = P.N;
-  const double la = 1.56, lb = 1.64, dT = P.dT;
+  const double dT = P.dT;
   double x[4] = {X[0], X[1], X[2], X[3]};
   // the trajectory is written a knot group at a time: every lane holds the whole state, lane sub
   // keeps knot j of X and knot i of U with j, i = sub (mod 4), and after each 4th knot the quad
@@ -946,21 +977,11 @@ __device__ double forward_trial_quad(const IlqrDev& P, const double* X, const do
   // knot i's inputs were loaded during knot i-1 (the loads are off the x chain; loading them at the
   // top of the knot put an L2 round trip on it)
   double xr[4], Kr[8], kr[2], ur[2];
-#pragma unroll
-  for (int r = 0; r < 4; r++) xr[r] = X[r];
-#pragma unroll
-  for (int r = 0; r < 8; r++) Kr[r] = Kg[r];
-  kr[0] = k[0]; kr[1] = k[1];
-  ur[0] = U[0]; ur[1] = U[1];
+  knot_load(X, U, k, Kg, 0, xr, Kr, kr, ur);
   for (int i = 0; i < N - 1; i++) {
     const int in = i + 2 < N ? i + 1 : i;  // knot i+1 (clamped)
     double nxr[4], nK[8], nk[2], nu[2];
-#pragma unroll
-    for (int r = 0; r < 4; r++) nxr[r] = X[4 * in + r];
-#pragma unroll
-    for (int r = 0; r < 8; r++) nK[r] = Kg[8 * in + r];
-    nk[0] = k[2 * in]; nk[1] = k[2 * in + 1];
-    nu[0] = U[2 * in]; nu[1] = U[2 * in + 1];
+    knot_load(X, U, k, Kg, in, nxr, nK, nk, nu);
     double dx[4], u[2];
 #pragma unroll
     for (int r = 0; r < 4; r++) dx[r] = x[r] - xr[r];
@@ -985,25 +1006,14 @@ __device__ double forward_trial_quad(const IlqrDev& P, const double* X, const do
     // RK4Integration with the stage sincos spread over the quad
     const UPre q = upre(u[1]);
     const double ax = u[0];
-    const double k1_3 = x[2] * q.cb * q.tdl / (la + lb);
-    const double x2_2 = x[2] + dT / 2 * ax, x2_3 = x[3] + dT / 2 * k1_3;
-    const double k2_3 = x2_2 * q.cb * q.tdl / (la + lb);
-    const double x3_2 = x[2] + dT / 2 * ax, x3_3 = x[3] + dT / 2 * k2_3;
-    const double k3_3 = x3_2 * q.cb * q.tdl / (la + lb);
-    const double x4_2 = x[2] + dT * ax, x4_3 = x[3] + dT * k3_3;
-    const double k4_3 = x4_2 * q.cb * q.tdl / (la + lb);
-    const double hd = sub == 0 ? x[3] : sub == 1 ? x2_3 : sub == 2 ? x3_3 : x4_3;
+    const Rk4Heads h(x, ax, q, dT);
+    const double hd = sub == 0 ? x[3] : sub == 1 ? h.x2_3 : sub == 2 ? h.x3_3 : h.x4_3;
     double sn, cs;
     mpj_sincos(hd + q.beta, &sn, &cs);
-    const double s1 = quad_bcast<0>(sn), c1 = quad_bcast<0>(cs), s2 = quad_bcast<1>(sn), c2 = quad_bcast<1>(cs);
-    const double s3 = quad_bcast<2>(sn), c3 = quad_bcast<2>(cs), s4 = quad_bcast<3>(sn), c4 = quad_bcast<3>(cs);
-    const double k1[4] = {x[2] * c1, x[2] * s1, ax, k1_3};
-    const double k2[4] = {x2_2 * c2, x2_2 * s2, ax, k2_3};
-    const double k3[4] = {x3_2 * c3, x3_2 * s3, ax, k3_3};
-    const double k4[4] = {x4_2 * c4, x4_2 * s4, ax, k4_3};
+    const double sc[8] = {quad_bcast<0>(sn), quad_bcast<0>(cs), quad_bcast<1>(sn), quad_bcast<1>(cs),
+                          quad_bcast<2>(sn), quad_bcast<2>(cs), quad_bcast<3>(sn), quad_bcast<3>(cs)};
     double xn[4];
-#pragma unroll
-    for (int r = 0; r < 4; r++) xn[r] = 1.0 / 6 * (k1[r] + 2 * k2[r] + 2 * k3[r] + k4[r]) * dT + x[r];
+    h.combine(x, ax, dT, sc, xn);
 #pragma unroll
     for (int r = 0; r < 4; r++) x[r] = xn[r];
     if (((i + 1) & 3) == sub) {
@@ -1056,28 +1066,18 @@ __device__ __forceinline__ double pair_bcast(double v) {
 __device__ double forward_trial_pair(const IlqrDev& P, const double* X, const double* U, const double* k,
                                      const double* Kg, double alpha, double* Xn, double* Un, bool wr, int sub) {
   const int N = P.N;
-  const double la = 1.56, lb = 1.64, dT = P.dT;
+  const double dT = P.dT;
   double x[4] = {X[0], X[1], X[2], X[3]};
   double sx[2][4], su[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
 #pragma unroll
   for (int r = 0; r < 4; r++) sx[0][r] = sx[1][r] = x[r];
   double J = 0.0;
   double xr[4], Kr[8], kr[2], ur[2];
-#pragma unroll
-  for (int r = 0; r < 4; r++) xr[r] = X[r];
-#pragma unroll
-  for (int r = 0; r < 8; r++) Kr[r] = Kg[r];
-  kr[0] = k[0]; kr[1] = k[1];
-  ur[0] = U[0]; ur[1] = U[1];
+  knot_load(X, U, k, Kg, 0, xr, Kr, kr, ur);
   for (int i = 0; i < N - 1; i++) {
     const int in = i + 2 < N ? i + 1 : i;  // knot i+1 (clamped)
     double nxr[4], nK[8], nk[2], nu[2];
-#pragma unroll
-    for (int r = 0; r < 4; r++) nxr[r] = X[4 * in + r];
-#pragma unroll
-    for (int r = 0; r < 8; r++) nK[r] = Kg[8 * in + r];
-    nk[0] = k[2 * in]; nk[1] = k[2 * in + 1];
-    nu[0] = U[2 * in]; nu[1] = U[2 * in + 1];
+    knot_load(X, U, k, Kg, in, nxr, nK, nk, nu);
     double dx[4], u[2];
 #pragma unroll
     for (int r = 0; r < 4; r++) dx[r] = x[r] - xr[r];
@@ -1104,25 +1104,14 @@ __device__ double forward_trial_pair(const IlqrDev& P, const double* X, const do
     }
     const UPre q = upre(u[1]);
     const double ax = u[0];
-    const double k1_3 = x[2] * q.cb * q.tdl / (la + lb);
-    const double x2_2 = x[2] + dT / 2 * ax, x2_3 = x[3] + dT / 2 * k1_3;
-    const double k2_3 = x2_2 * q.cb * q.tdl / (la + lb);
-    const double x3_2 = x[2] + dT / 2 * ax, x3_3 = x[3] + dT / 2 * k2_3;
-    const double k3_3 = x3_2 * q.cb * q.tdl / (la + lb);
-    const double x4_2 = x[2] + dT * ax, x4_3 = x[3] + dT * k3_3;
-    const double k4_3 = x4_2 * q.cb * q.tdl / (la + lb);
+    const Rk4Heads h(x, ax, q, dT);
     double snA, csA, snB, csB;
-    mpj_sincos((sub ? x2_3 : x[3]) + q.beta, &snA, &csA);  // stage 1 / 2
-    mpj_sincos((sub ? x4_3 : x3_3) + q.beta, &snB, &csB);  // stage 3 / 4
-    const double s1 = pair_bcast<0>(snA), c1 = pair_bcast<0>(csA), s2 = pair_bcast<1>(snA), c2 = pair_bcast<1>(csA);
-    const double s3 = pair_bcast<0>(snB), c3 = pair_bcast<0>(csB), s4 = pair_bcast<1>(snB), c4 = pair_bcast<1>(csB);
-    const double k1[4] = {x[2] * c1, x[2] * s1, ax, k1_3};
-    const double k2[4] = {x2_2 * c2, x2_2 * s2, ax, k2_3};
-    const double k3[4] = {x3_2 * c3, x3_2 * s3, ax, k3_3};
-    const double k4[4] = {x4_2 * c4, x4_2 * s4, ax, k4_3};
+    mpj_sincos((sub ? h.x2_3 : x[3]) + q.beta, &snA, &csA);  // stage 1 / 2
+    mpj_sincos((sub ? h.x4_3 : h.x3_3) + q.beta, &snB, &csB);  // stage 3 / 4
+    const double sc[8] = {pair_bcast<0>(snA), pair_bcast<0>(csA), pair_bcast<1>(snA), pair_bcast<1>(csA),
+                          pair_bcast<0>(snB), pair_bcast<0>(csB), pair_bcast<1>(snB), pair_bcast<1>(csB)};
     double xn[4];
-#pragma unroll
-    for (int r = 0; r < 4; r++) xn[r] = 1.0 / 6 * (k1[r] + 2 * k2[r] + 2 * k3[r] + k4[r]) * dT + x[r];
+    h.combine(x, ax, dT, sc, xn);
 #pragma unroll
     for (int r = 0; r < 4; r++) x[r] = xn[r];
     if ((((i + 1) & 3) >> 1) == sub) {
@@ -1559,12 +1548,9 @@ int run_backward(mp_ctx* ctx, const IlqrDev& D, int B, const double* dX, const d
   double* dD = (double*)mp_ws(ctx, WS_ILQR0, sizeof(double) * (size_t)B * (D.N - 1) * ND);  // knot stride ND*B
   if (!dD) return MP_ERR_NOMEM;
   mp_time_begin(ctx);  // the timed region covers both kernels of the backward pass
-  if (na <= kDeriv4Max)  // few active instances: four lanes per record (latency-bound launch)
-    hipLaunchKernelGGL(ilqr_deriv4_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, ctx->stream, D, B, dX,
-                       dU, list, n_dev, na, dD);
-  else
-    hipLaunchKernelGGL(ilqr_deriv_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, D, B, dX, dU,
-                       list, n_dev, na, dD);
+  // few active instances: four lanes per record (latency-bound launch)
+  hipLaunchKernelGGL(ilqr_deriv4_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, ctx->stream, D, B, dX, dU,
+                     list, n_dev, na, dD);
   MP_HIP(ctx, hipGetLastError());
   hipLaunchKernelGGL(ilqr_backward_quad_kernel, dim3((na + kQuadIPB - 1) / kQuadIPB), dim3(128),
                      sizeof(double) * 2 * ND * kQuadIPB, ctx->stream, D, B, dX, dD, list, n_dev, na, dk, dK);
@@ -1573,17 +1559,278 @@ int run_backward(mp_ctx* ctx, const IlqrDev& D, int B, const double* dX, const d
   return MP_OK;
 }
 
+// the entry points' shared prologue: the context, the parameters, the caller's pointers
+int ilqr_enter(mp_ctx* ctx, const mp_ilqr_params* p, int B, IlqrDev* D, bool pointers) {
+  if (!ctx) return MP_ERR_INVALID;
+  if (int st = make_ilqr(ctx, p, B, D)) return st;
+  MP_CHECK(ctx, pointers, "required pointer is NULL");
+  return MP_OK;
+}
+
+// mp_ilqr_forward / mp_ilqr_forward_dev: one trial per instance at its own alpha, device pointers
+int launch_forward(mp_ctx* ctx, const IlqrDev& D, int B, const double* X, const double* U, const double* k,
+                   const double* Kg, const double* alpha, double* Xnew, double* Unew, double* Jnew) {
+  mp_time_begin(ctx);
+  hipLaunchKernelGGL(ilqr_forward_quad_kernel, dim3((B + 15) / 16), dim3(64), 0, ctx->stream, D, B, X, U, k, Kg,
+                     alpha, Xnew, Unew, Jnew);
+  MP_HIP(ctx, hipGetLastError());
+  mp_time_end(ctx);
+  return MP_OK;
+}
+
+// mp_ilqr_solve's host side, from here to ilqr_solve.  The plan's (ilqr_plan.hpp) second step, the workspace:
+// rest slots only while they also fit in half (X) and a quarter (U) of the free device memory and the
+// context's workspace cap; without them -- or when allocating them fails -- the G-wide kernel runs its rounds
+// to the end: the same accepted trials (tests/test_gpu_ilqr.py), more latency.
+int ilqr_ws_acquire(mp_ctx* ctx, const IlqrDev& D, int B, double* X, double* U, bool dev, IlqrPlan* P, IlqrWs* W) {
+  const size_t N = D.N;
+  const IlqrWsBytes z = ilqr_ws_bytes(B, N, *P);
+  int st = MP_OK;
+  W->X = dev ? X : (double*)mp_upload(ctx, WS_IO0, X, 4 * N * B, &st);
+  W->U = dev ? U : (double*)mp_upload(ctx, WS_IO1, U, 2 * N * B, &st);
+  W->k = (double*)mp_ws(ctx, WS_IO2, z.k);
+  W->K = (double*)mp_ws(ctx, WS_IO3, z.K);
+  W->Xn = (double*)mp_ws(ctx, WS_IO4, z.Xn);
+  W->Un = (double*)mp_ws(ctx, WS_IO5, z.Un);
+  W->J = (double*)mp_ws(ctx, WS_IO6, z.J);
+  int* ints = (int*)mp_ws(ctx, WS_IO7, z.ints);
+  if (st || !W->k || !W->K || !W->Xn || !W->Un || !W->J || !ints) return st ? st : MP_ERR_NOMEM;
+  P->rest = P->rest && mp_ws_affordable(ctx, WS_ILQR1, z.Xs, 0.5) && mp_ws_affordable(ctx, WS_ILQR2, z.Us, 0.25);
+  W->Xs = W->Us = W->Jt = nullptr;
+  int* pw = nullptr;
+  if (P->rest) {
+    W->Xs = (double*)mp_ws(ctx, WS_ILQR1, z.Xs);
+    W->Us = W->Xs ? (double*)mp_ws(ctx, WS_ILQR2, z.Us) : nullptr;
+    W->Jt = W->Us ? (double*)mp_ws(ctx, WS_IO12, z.Jt) : nullptr;
+    pw = W->Jt ? (int*)mp_ws(ctx, WS_IO13, z.pw) : nullptr;
+    if (!pw) {           // one of the four failed: fall back to the multi-round 16-wide search
+      P->rest = false;   // (the failed allocation left a message; mp_ws already cleared the HIP error)
+      ctx->err.clear();
+    }
+  }
+  ilqr_ws_map(W, B, ints, pw);
+  return MP_OK;
+}
+
+// The count report.  The host runs one iteration ahead: after enqueueing iteration t it learns the counts after
+// t-1 -- the instances the pipelined round 0 left pending (their rest pass runs in the next launch, then they
+// rejoin the list) plus the list count -- which bound iteration t+1's active count, so the GPU never idles
+// between iterations while the host waits.  Launch grids are sized by that bound (n_act); the derivative and
+// sweep kernels read the exact count on the device, the search kernels skip inactive instances; once the
+// counts read 0 the iteration just enqueued was a no-op.  Two ways to learn them: host memory that the next
+// backward pass's first kernel writes (ilqr_mirror; 0.3-0.5 ms per 4096-instance solve less than a stream copy
+// and event per iteration, r05zd), or, for a context without mapped host memory, that copy and event.
+struct IlqrCounts {
+  mp_ctx* ctx;
+  int n_act;                                   // upper bound on the active count of the iteration being enqueued
+  hipEvent_t ev[2] = {nullptr, nullptr};       // copy path: iteration parity q's counts have landed in hn
+  int* hn = nullptr;                           // pinned, hn[2q] = pending, hn[2q + 1] = list count
+  volatile unsigned long long* hmr = nullptr;  // mirror path: (seq << 32) | list count, (seq << 32) | pending
+  unsigned long long* dmr = nullptr;           // ... and the device's address of them
+
+  IlqrCounts(mp_ctx* c, int B) : ctx(c), n_act(B) {}
+  ~IlqrCounts() { for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x); }
+  int init() {
+    if (!(hn = (int*)mp_pinned(ctx, 4 * sizeof(int)))) return mp_fail(ctx, MP_ERR_NOMEM, "pinned allocation failed");
+    for (int q = 0; q < 2; q++) MP_HIP(ctx, hipEventCreateWithFlags(&ev[q], hipEventDisableTiming));
+    if ((hmr = mp_mapped(ctx, &dmr))) hmr[0] = hmr[1] = 0;
+    return MP_OK;
+  }
+  // iteration outer's backward pass reports the previous search's counts with seq = outer (0 = none yet)
+  IlqrDev stamp(IlqrDev D, int outer) const {
+    if (hmr && outer > 0) D.mirror = dmr, D.mirror_seq = outer;
+    return D;
+  }
+  // After enqueueing iteration outer, whose search writes counts[0..1]: learn the counts after outer - 1,
+  // *stop if they are zero.
+  int report(int outer, const int* counts, bool* stop) {
+    *stop = false;
+    int nprev = 0;
+    if (int st = hmr ? wait_mirror(outer, &nprev) : wait_copy(outer, counts, &nprev)) return st;
+    if (outer == 0) return MP_OK;  // nothing to learn yet
+    if (nprev == 0) *stop = true;
+    else n_act = nprev;
+    return MP_OK;
+  }
+  int wait_mirror(int outer, int* nprev) {
+    if (outer == 0) return MP_OK;
+    const unsigned long long want = (unsigned long long)(unsigned)outer;  // seq = (iteration outer - 1) + 1
+    unsigned long long a = hmr[0], pd = hmr[1];  // (each word carries its seq: no order between them)
+    long long spins = 0;
+    while ((a >> 32) < want || (pd >> 32) < want) {
+      if ((++spins & 1023) == 0) {
+        const hipError_t q = hipStreamQuery(ctx->stream);
+        if (q != hipErrorNotReady) {
+          // the stream is idle (or failed): the kernel's stores are visible now, so one more read decides
+          a = hmr[0], pd = hmr[1];
+          if ((a >> 32) >= want && (pd >> 32) >= want) break;
+          if (q != hipSuccess) return mp_fail(ctx, MP_ERR_HIP, "iLQR solve stream failed: %s", hipGetErrorString(q));
+          return mp_fail(ctx, MP_ERR_HIP, "iLQR count mirror never arrived");
+        }
+      }
+      a = hmr[0], pd = hmr[1];
+    }
+    *nprev = (int)(a & 0xffffffffu) + (int)(pd & 0xffffffffu);
+    return MP_OK;
+  }
+  int wait_copy(int outer, const int* counts, int* nprev) {
+    MP_HIP(ctx, hipMemcpyAsync(hn + 2 * (outer & 1), counts, 2 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    MP_HIP(ctx, hipEventRecord(ev[outer & 1], ctx->stream));
+    if (outer == 0) return MP_OK;
+    MP_HIP(ctx, hipEventSynchronize(ev[(outer - 1) & 1]));
+    *nprev = hn[2 * ((outer - 1) & 1)] + hn[2 * ((outer - 1) & 1) + 1];
+    return MP_OK;
+  }
+};
+
+// One solve: what its parts share, and the parts.  Iteration outer's search writes W.list[outer & 1] ([0] pending
+// count, [1] list count); its finish kernel zeroes the counts of the other list, which the next iteration writes.
+struct IlqrSolve {
+  mp_ctx* ctx;
+  IlqrDev D;
+  int B;
+  IlqrPlan plan;
+  IlqrWs W;
+  IlqrLoop L;
+
+  // blocks along y (one-pass) or after round 0's (pipelined) for T2 trials of kSearchL lanes each
+  unsigned rest_cols() const { return (unsigned)((plan.T2 + 64 / kSearchL - 1) / (64 / kSearchL)); }
+
+  // both lists' counts zero, every instance active in list[1] (iteration 0's backward pass reads it); with rest
+  // slots pend[2][B] = 0 and winm[2][B] = 0x7f7f7f7f: afterwards the finish kernels reset what they use
+  int begin() {
+    MP_HIP(ctx, hipMemsetAsync(W.list[0], 0, 2 * sizeof(int), ctx->stream));
+    MP_HIP(ctx, hipMemsetAsync(W.list[1], 0, 2 * sizeof(int), ctx->stream));
+    hipLaunchKernelGGL(ilqr_init_kernel, dim3((B + 63) / 64), dim3(64), 0, ctx->stream, D, B, W.X, W.U, W.J, W.active,
+                       W.iters, W.flags, W.list[1] + 2);
+    MP_HIP(ctx, hipGetLastError());
+    if (plan.rest) {
+      MP_HIP(ctx, hipMemsetAsync(W.pend[0], 0, sizeof(int) * 2 * B, ctx->stream));
+      MP_HIP(ctx, hipMemsetAsync(W.winm[0], 0x7f, sizeof(int) * 2 * B, ctx->stream));
+    }
+    return MP_OK;
+  }
+
+  // One pass: every active instance's trials 0..min(m*, ls_cap) in one launch (m* = 51..75 measured, so ~4
+  // waves per instance) -- the round-0 latency chain and the rest chain become one.
+  int enqueue_onepass(int outer) {
+    int *wr = W.list[outer & 1], *zn = W.list[(outer + 1) & 1];
+    if (!L.onepass) MP_HIP(ctx, hipMemsetAsync(W.winm1, 0x7f, sizeof(int) * B, ctx->stream));
+    L.onepass = true;
+    hipLaunchKernelGGL((ilqr_search_rest_kernel<kSearchG, kSearchL>), dim3((unsigned)B, rest_cols()), dim3(64), 0,
+                       ctx->stream, D, B, W.X, W.U, W.k, W.K, W.J, W.active, W.mstar1, W.Xs, W.Us, W.Jt, W.winm1, 0,
+                       plan.T2);
+    MP_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(ilqr_search_finish_kernel<kSearchG>, dim3((unsigned)B), dim3(64), 0, ctx->stream, D, B, W.X, W.U,
+                       W.active, W.mstar1, W.Xs, W.Us, W.Jt, W.winm1, W.J, W.active, W.iters, W.flags, wr + 1, 0,
+                       plan.T2, 2, zn);
+    MP_HIP(ctx, hipGetLastError());
+    L.counts_zero = true;
+    return MP_OK;
+  }
+
+  // Pipelined two passes (ilqr_search_pipe_kernel): round 0 on a lane pair per trial while at least kPairMin
+  // instances are active (throughput-bound), else on a lane quad (4 waves per SIMD at B = 4096)
+  int enqueue_pipelined(int outer, int n_act) {
+    int *wr = W.list[outer & 1], *zn = W.list[(outer + 1) & 1];
+    const int l0 = n_act >= kPairMin ? kRound0L : kSearchL, ipw = 64 / (kSearchG * l0);
+    const unsigned g0 = (unsigned)((B + ipw - 1) / ipw);
+    const int cur = L.q2 & 1, old = cur ^ 1;
+    L.q2++;
+    auto pipe_k = l0 == kRound0L ? ilqr_search_pipe_kernel<kSearchG, kSearchL, kRound0L>
+                                 : ilqr_search_pipe_kernel<kSearchG, kSearchL, kSearchL>;
+    hipLaunchKernelGGL(pipe_k, dim3(g0 + (unsigned)B * rest_cols()), dim3(64), 0, ctx->stream, D, B, W.X, W.U, W.k,
+                       W.K, W.Xn, W.Un, W.J, W.active, W.iters, W.flags, wr + 1, W.pend[cur], W.mstar[cur], wr,
+                       W.pend[old], W.mstar[old], W.Xs, W.Us, W.Jt, W.winm[old], plan.T2, (int)g0);
+    MP_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(ilqr_search_finish_kernel<kSearchG>, dim3((unsigned)B), dim3(64), 0, ctx->stream, D, B, W.X, W.U,
+                       W.pend[old], W.mstar[old], W.Xs, W.Us, W.Jt, W.winm[old], W.J, W.active, W.iters, W.flags,
+                       wr + 1, kSearchG, plan.T2, 3, zn);
+    MP_HIP(ctx, hipGetLastError());
+    L.counts_zero = true;
+    return MP_OK;
+  }
+
+  // No rest slots: the G-wide kernel runs its rounds to the end (G = 16 on lane quads, the narrower one lane)
+  int enqueue_rounds(int outer) {
+    const int G = plan.G, ipw = G == kSearchG ? 64 / (kSearchG * kSearchL) : 64 / G;
+    auto search_k = ilqr_search_kernel<kSearchG, kSearchL>;
+    if (G != kSearchG) search_k = G == 4 ? ilqr_search_kernel<4> : ilqr_search_kernel<1>;
+    hipLaunchKernelGGL(search_k, dim3((unsigned)((B + ipw - 1) / ipw)), dim3(64), 0, ctx->stream, D, B, W.X, W.U, W.k,
+                       W.K, W.Xn, W.Un, W.J, W.active, W.iters, W.flags, W.list[outer & 1] + 1, 0, nullptr, nullptr);
+    MP_HIP(ctx, hipGetLastError());
+    return MP_OK;
+  }
+
+  // The results: device to device or downloaded, then the flags and their two verdicts
+  int read_back(double* X, double* U, double* J, int32_t* iters, bool dev) {
+    const size_t N = D.N, n = B;
+    int st;
+    std::vector<int> hfl(n);
+    if (dev) {  // X / U are already the caller's; J and the iteration counts device to device
+      MP_HIP(ctx, hipMemcpyAsync(J, W.J, sizeof(double) * n, hipMemcpyDeviceToDevice, ctx->stream));
+      MP_HIP(ctx, hipMemcpyAsync(iters, W.iters, sizeof(int) * n, hipMemcpyDeviceToDevice, ctx->stream));
+    } else {
+      if ((st = mp_download(ctx, X, (const double*)W.X, 4 * N * n))) return st;
+      if ((st = mp_download(ctx, U, (const double*)W.U, 2 * N * n))) return st;
+      if ((st = mp_download(ctx, J, (const double*)W.J, n))) return st;
+      if ((st = mp_download(ctx, iters, (const int*)W.iters, n))) return st;
+    }
+    if ((st = mp_download(ctx, hfl.data(), (const int*)W.flags, n))) return st;
+    MP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    int any = 0;
+    for (int f : hfl) any |= f;
+    if (any & 1) return mp_fail(ctx, MP_ERR_NUMERIC, "line search hit max_ls for some instance (the reference would loop forever)");
+    if (any & 2) return mp_fail(ctx, MP_ERR_NUMERIC, "max_iter reached before |dJ/J| <= tol for some instance");
+    return MP_OK;
+  }
+};
+
+// mp_ilqr_solve (dev = false: host X / U / J / iters, uploaded and downloaded here) and mp_ilqr_solve_dev (dev:
+// the caller's device buffers, X / U solved in place)
+int ilqr_solve(mp_ctx* ctx, const mp_ilqr_params* p, int32_t B, double* X, double* U, double* J, int32_t* iters,
+               bool dev) {
+  IlqrDev D;
+  int st = ilqr_enter(ctx, p, B, &D, X && U && J && iters);
+  if (st) return st;
+  MP_HIP(ctx, hipSetDevice(ctx->device));
+  IlqrSolve S{ctx, D, B, ilqr_plan(B, D.N, D.ls_cap, ctx->ws_limit, kSearchG)};
+  if ((st = ilqr_ws_acquire(ctx, S.D, B, X, U, dev, &S.plan, &S.W))) return st;
+  if ((st = S.begin())) return st;
+  IlqrCounts cnt(ctx, B);
+  if ((st = cnt.init())) return st;
+  // (an instance in a rest pass sits one launch out, so the pipelined loop may take more launches than
+  // max_iter + 2; each instance still stops at its own max_iter)
+  for (int outer = 0; outer <= 2 * (S.D.max_iter + 2); outer++) {
+    // the backward pass covers the active instances only: the compact list the previous iteration wrote (or
+    // the init kernel), while this iteration's search writes the other
+    int *rd = S.W.list[(outer + 1) & 1], *wr = S.W.list[outer & 1];
+    if ((st = run_backward(ctx, cnt.stamp(S.D, outer), B, S.W.X, S.W.U, rd + 2, rd + 1, cnt.n_act, S.W.k, S.W.K)))
+      return st;
+    if (!S.L.counts_zero) MP_HIP(ctx, hipMemsetAsync(wr, 0, 2 * sizeof(int), ctx->stream));
+    S.L.counts_zero = false;
+    mp_time_begin(ctx);
+    if (S.plan.rest && (S.L.onepass || cnt.n_act <= kOnePassMax)) st = S.enqueue_onepass(outer);
+    else if (S.plan.rest) st = S.enqueue_pipelined(outer, cnt.n_act);
+    else st = S.enqueue_rounds(outer);
+    if (st) return st;
+    mp_time_end(ctx);
+    bool stop;
+    if ((st = cnt.report(outer, wr, &stop))) return st;
+    if (stop) break;
+  }
+  return S.read_back(X, U, J, iters, dev);
+}
+
 }  // namespace
 
 extern "C" {
 
 int mp_ilqr_rollout(mp_ctx* ctx, const mp_ilqr_params* p, int32_t B, const double* x0, const double* U, double* X,
                     double* J) {
-  if (!ctx) return MP_ERR_INVALID;
   IlqrDev D;
-  int st = make_ilqr(ctx, p, B, &D);
+  int st = ilqr_enter(ctx, p, B, &D, x0 && U && X && J);
   if (st) return st;
-  MP_CHECK(ctx, x0 && U && X && J, "required pointer is NULL");
   MP_HIP(ctx, hipSetDevice(ctx->device));
   const size_t N = D.N;
   const double* dx0 = mp_upload(ctx, WS_IO0, x0, 4 * (size_t)B, &st);
@@ -1601,11 +1848,9 @@ int mp_ilqr_rollout(mp_ctx* ctx, const mp_ilqr_params* p, int32_t B, const doubl
 
 int mp_ilqr_backward(mp_ctx* ctx, const mp_ilqr_params* p, int32_t B, const double* X, const double* U, double* k,
                      double* Kg) {
-  if (!ctx) return MP_ERR_INVALID;
   IlqrDev D;
-  int st = make_ilqr(ctx, p, B, &D);
+  int st = ilqr_enter(ctx, p, B, &D, X && U && k && Kg);
   if (st) return st;
-  MP_CHECK(ctx, X && U && k && Kg, "required pointer is NULL");
   MP_HIP(ctx, hipSetDevice(ctx->device));
   const size_t N = D.N;
   const double* dX = mp_upload(ctx, WS_IO0, X, 4 * N * B, &st);
@@ -1623,11 +1868,9 @@ int mp_ilqr_backward(mp_ctx* ctx, const mp_ilqr_params* p, int32_t B, const doub
 int mp_ilqr_forward(mp_ctx* ctx, const mp_ilqr_params* p, int32_t B, const double* X, const double* U,
                     const double* k, const double* Kg, const double* alpha, double* Xnew, double* Unew,
                     double* Jnew) {
-  if (!ctx) return MP_ERR_INVALID;
   IlqrDev D;
-  int st = make_ilqr(ctx, p, B, &D);
+  int st = ilqr_enter(ctx, p, B, &D, X && U && k && Kg && alpha && Xnew && Unew && Jnew);
   if (st) return st;
-  MP_CHECK(ctx, X && U && k && Kg && alpha && Xnew && Unew && Jnew, "required pointer is NULL");
   MP_HIP(ctx, hipSetDevice(ctx->device));
   const size_t N = D.N;
   const double* dX = mp_upload(ctx, WS_IO0, X, 4 * N * B, &st);
@@ -1639,11 +1882,7 @@ int mp_ilqr_forward(mp_ctx* ctx, const mp_ilqr_params* p, int32_t B, const doubl
   double* dUn = mp_alloc_out(ctx, WS_IO6, Unew, 2 * N * B, &st);
   double* dJ = mp_alloc_out(ctx, WS_IO7, Jnew, (size_t)B, &st);
   if (st) return st;
-  mp_time_begin(ctx);
-  hipLaunchKernelGGL(ilqr_forward_quad_kernel, dim3((B + 15) / 16), dim3(64), 0, ctx->stream, D, B, dX, dU, dk, dK,
-                     da, dXn, dUn, dJ);
-  MP_HIP(ctx, hipGetLastError());
-  mp_time_end(ctx);
+  if ((st = launch_forward(ctx, D, B, dX, dU, dk, dK, da, dXn, dUn, dJ))) return st;
   if ((st = mp_download(ctx, Xnew, (const double*)dXn, 4 * N * B))) return st;
   if ((st = mp_download(ctx, Unew, (const double*)dUn, 2 * N * B))) return st;
   if ((st = mp_download(ctx, Jnew, (const double*)dJ, (size_t)B))) return st;
@@ -1653,263 +1892,17 @@ int mp_ilqr_forward(mp_ctx* ctx, const mp_ilqr_params* p, int32_t B, const doubl
 
 int mp_ilqr_backward_dev(mp_ctx* ctx, const mp_ilqr_params* p, int32_t B, const double* X, const double* U,
                          double* k, double* Kg) {
-  if (!ctx) return MP_ERR_INVALID;
   IlqrDev D;
-  int st = make_ilqr(ctx, p, B, &D);
-  if (st) return st;
-  MP_CHECK(ctx, X && U && k && Kg, "required pointer is NULL");
+  if (int st = ilqr_enter(ctx, p, B, &D, X && U && k && Kg)) return st;
   return run_backward(ctx, D, B, X, U, nullptr, nullptr, B, k, Kg);
 }
 
 int mp_ilqr_forward_dev(mp_ctx* ctx, const mp_ilqr_params* p, int32_t B, const double* X, const double* U,
                         const double* k, const double* Kg, const double* alpha, double* Xnew, double* Unew,
                         double* Jnew) {
-  if (!ctx) return MP_ERR_INVALID;
   IlqrDev D;
-  int st = make_ilqr(ctx, p, B, &D);
-  if (st) return st;
-  MP_CHECK(ctx, X && U && k && Kg && alpha && Xnew && Unew && Jnew, "required pointer is NULL");
-  mp_time_begin(ctx);
-  hipLaunchKernelGGL(ilqr_forward_quad_kernel, dim3((B + 15) / 16), dim3(64), 0, ctx->stream, D, B, X, U, k, Kg,
-                     alpha, Xnew, Unew, Jnew);
-  MP_HIP(ctx, hipGetLastError());
-  mp_time_end(ctx);
-  return MP_OK;
-}
-
-// mp_ilqr_solve (dev = false: host X / U / J / iters, uploaded and downloaded here) and mp_ilqr_solve_dev (dev:
-// the caller's device buffers, X / U solved in place)
-static int ilqr_solve(mp_ctx* ctx, const mp_ilqr_params* p, int32_t B, double* X, double* U, double* J,
-                      int32_t* iters, bool dev) {
-  if (!ctx) return MP_ERR_INVALID;
-  IlqrDev D;
-  int st = make_ilqr(ctx, p, B, &D);
-  if (st) return st;
-  MP_CHECK(ctx, X && U && J && iters, "required pointer is NULL");
-  MP_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t N = D.N;
-  double* dX = dev ? X : (double*)mp_upload(ctx, WS_IO0, X, 4 * N * B, &st);
-  double* dU = dev ? U : (double*)mp_upload(ctx, WS_IO1, U, 2 * N * B, &st);
-  double* dk = (double*)mp_ws(ctx, WS_IO2, sizeof(double) * 2 * (N - 1) * B);
-  double* dK = (double*)mp_ws(ctx, WS_IO3, sizeof(double) * 8 * (N - 1) * B);
-  // trial slots for the G-wide line search: G = kSearchG = 16 trials per instance on lane quads
-  // (4096 waves at B = 4096) while the slots stay within 1 GiB of HBM (and the context's workspace
-  // cap), else 4 single-lane trials, else 1 (the sequential loop)
-  auto fits = [&](size_t g) {  // X slots 32 B, U slots 16 B per (trial, instance, knot)
-    return g * B * N * 48 <= ((size_t)1 << 30) && (!ctx->ws_limit || g * B * N * 32 <= ctx->ws_limit);
-  };
-  const int G = fits(kSearchG) ? kSearchG : fits(4) ? 4 : 1;
-  double* dXn = (double*)mp_ws(ctx, WS_IO4, sizeof(double) * 4 * N * B * G);
-  double* dUn = (double*)mp_ws(ctx, WS_IO5, sizeof(double) * 2 * N * B * G);
-  double* dJ = (double*)mp_ws(ctx, WS_IO6, sizeof(double) * B);
-  int* dint = (int*)mp_ws(ctx, WS_IO7, sizeof(int) * (5 * (size_t)B + 4));
-  if (st || !dk || !dK || !dXn || !dUn || !dJ || !dint) return st ? st : MP_ERR_NOMEM;
-  int* dact = dint;
-  int* dit = dint + B;
-  int* dfl = dint + 2 * B;
-  // two list buffers, [0] instances the pipelined round 0 left pending, [1] active count, [2 ..] their compact
-  // list (search_accept): iteration q's backward pass reads par[(q + 1) & 1], its search writes par[q & 1],
-  // whose counts the finish kernel of iteration q - 1 zeroed (a memset only after a path without one)
-  int* par[2] = {dint + 3 * (size_t)B, dint + 3 * (size_t)B + (2 + (size_t)B)};
-  int* dnp = par[0];
-  int* dn = dnp + 1;
-  // trials G..ls_cap in one pass for the instances still searching after round 0 (G = kSearchG only),
-  // while their slots fit in 8 GiB, in half of the free device memory and in the context's
-  // workspace cap.  Otherwise -- or when allocating them fails -- the G-wide kernel runs its
-  // rounds to the end: the same accepted trials (tests/test_gpu_ilqr.py), more latency.
-  // Slots for trials 0..ls_cap, so that the same buffers serve the one-pass search (below).
-  const size_t T2 = G == kSearchG && D.ls_cap + 1 > G ? (size_t)(D.ls_cap + 1) : 0;
-  bool rest = T2 > 0 && T2 * B * N * 48 <= ((size_t)8 << 30) &&
-              mp_ws_affordable(ctx, WS_ILQR1, sizeof(double) * 4 * N * B * T2, 0.5) &&
-              mp_ws_affordable(ctx, WS_ILQR2, sizeof(double) * 2 * N * B * T2, 0.25);
-  double *dXs2 = nullptr, *dUs2 = nullptr, *dJt = nullptr;
-  // pending[B], winm[B], mstar[B]; pipelined: pend[2][B], winm[2][B], mstar[2][B] at [0, 6B);
-  // the one-pass search has its own winm[B], mstar[B] at [6B, 8B), so it never reads a slot the
-  // pipelined launches left set
-  int* dpw = nullptr;
-  if (rest) {
-    dXs2 = (double*)mp_ws(ctx, WS_ILQR1, sizeof(double) * 4 * N * B * T2);
-    dUs2 = dXs2 ? (double*)mp_ws(ctx, WS_ILQR2, sizeof(double) * 2 * N * B * T2) : nullptr;
-    dJt = dUs2 ? (double*)mp_ws(ctx, WS_IO12, sizeof(double) * B * T2) : nullptr;
-    dpw = dJt ? (int*)mp_ws(ctx, WS_IO13, sizeof(int) * 8 * (size_t)B) : nullptr;
-    if (!dXs2 || !dUs2 || !dJt || !dpw) {
-      rest = false;      // fall back to the multi-round 16-wide search
-      ctx->err.clear();  // (the failed allocation left a message; mp_ws already cleared the HIP error)
-    }
-  }
-  const dim3 g1((B + 63) / 64), b1(64);
-  MP_HIP(ctx, hipMemsetAsync(par[0], 0, 2 * sizeof(int), ctx->stream));
-  MP_HIP(ctx, hipMemsetAsync(par[1], 0, 2 * sizeof(int), ctx->stream));
-  hipLaunchKernelGGL(ilqr_init_kernel, g1, b1, 0, ctx->stream, D, B, dX, dU, dJ, dact, dit, dfl, par[1] + 2);
-  MP_HIP(ctx, hipGetLastError());
-  int* hn = (int*)mp_pinned(ctx, 4 * sizeof(int));
-  if (!hn) return mp_fail(ctx, MP_ERR_NOMEM, "pinned allocation failed");
-  // One-pass search: once at most kOnePassMax instances are active (the host's last poll), every
-  // active instance's trials 0..min(m*, ls_cap) run in one launch (m* = 51..75 measured, so ~4
-  // waves per instance) -- the round-0 latency chain and the rest chain become one.
-  // The host runs one iteration ahead: after enqueueing iteration t it waits for the active count
-  // after t-1 (copied into hn[(t-1)&1], event-ordered), which bounds iteration t+1's count, so the
-  // GPU never idles between iterations while the host polls.  Launch grids are sized by that bound;
-  // the derivative and sweep kernels read the exact count (dn[0]) on the device, the search kernels
-  // skip inactive instances; once the count reads 0 the iteration just enqueued was a no-op.
-  struct EvPair {
-    hipEvent_t e[2] = {nullptr, nullptr};
-    ~EvPair() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-  } evp;
-  for (int q = 0; q < 2; q++) MP_HIP(ctx, hipEventCreateWithFlags(&evp.e[q], hipEventDisableTiming));
-  int n_act = B;  // upper bound on the active count of the iteration being enqueued
-  // hn[2q] = instances left pending by the pipelined round 0 (their rest pass runs in the next
-  // launch, then they rejoin the list), hn[2q + 1] = the list count: their sum bounds the next list
-  // the counts come from host memory the next backward pass's first kernel writes (ilqr_mirror) instead of a
-  // stream copy + event per iteration: 0.3-0.5 ms per 4096-instance solve (r05zd); the copy + event poll
-  // remains for a context without mapped host memory
-  unsigned long long* dmr = nullptr;
-  volatile unsigned long long* hmr = mp_mapped(ctx, &dmr);
-  if (hmr) hmr[0] = hmr[1] = 0;
-  auto poll = [&](int outer, bool* stop) -> int {
-    *stop = false;
-    if (hmr) {  // the counts of iteration outer - 1's search, reported by this iteration's backward pass
-      if (outer == 0) return MP_OK;
-      const unsigned long long want = (unsigned long long)(unsigned)(outer - 1 + 1);  // seq = iteration + 1
-      unsigned long long a = hmr[0], pd = hmr[1];  // (each word carries its seq: no order between them)
-      long long spins = 0;
-      while ((a >> 32) < want || (pd >> 32) < want) {
-        if ((++spins & 1023) == 0) {
-          const hipError_t q = hipStreamQuery(ctx->stream);
-          if (q != hipErrorNotReady) {
-            // the stream is idle (or failed): the kernel's stores are visible now, so one more read decides
-            a = hmr[0];
-            pd = hmr[1];
-            if ((a >> 32) >= want && (pd >> 32) >= want) break;
-            if (q != hipSuccess) return mp_fail(ctx, MP_ERR_HIP, "iLQR solve stream failed: %s", hipGetErrorString(q));
-            return mp_fail(ctx, MP_ERR_HIP, "iLQR count mirror never arrived");
-          }
-        }
-        a = hmr[0];
-        pd = hmr[1];
-      }
-      const int nprev = (int)(a & 0xffffffffu) + (int)(pd & 0xffffffffu);
-      if (nprev == 0) *stop = true;
-      else n_act = nprev;
-      return MP_OK;
-    }
-    MP_HIP(ctx, hipMemcpyAsync(hn + 2 * (outer & 1), dnp, 2 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    MP_HIP(ctx, hipEventRecord(evp.e[outer & 1], ctx->stream));
-    if (outer == 0) return MP_OK;
-    MP_HIP(ctx, hipEventSynchronize(evp.e[(outer - 1) & 1]));
-    const int nprev = hn[2 * ((outer - 1) & 1)] + hn[2 * ((outer - 1) & 1) + 1];
-    if (nprev == 0) *stop = true;
-    else n_act = nprev;
-    return MP_OK;
-  };
-  // pipelined two-pass search (ilqr_search_pipe_kernel): launch q marks pend[q & 1] and runs the rest
-  // pass of pend[(q - 1) & 1], so each rest pass overlaps the next iteration's round 0; pend[1] starts empty
-  int q2 = 0;  // two-pass launches so far
-  if (rest) {  // pend[2][B] = 0, winm[2][B] = 0x7f7f7f7f; afterwards the finish kernels reset what they use
-    MP_HIP(ctx, hipMemsetAsync(dpw, 0, sizeof(int) * 2 * B, ctx->stream));
-    MP_HIP(ctx, hipMemsetAsync(dpw + 2 * B, 0x7f, sizeof(int) * 2 * B, ctx->stream));
-  }
-  bool onepass_armed = false;  // winm of the one-pass search set (then reset by its finish kernels)
-  // (an instance in a rest pass sits one launch out, so the pipelined loop may take more launches
-  // than max_iter + 2; each instance still stops at its own max_iter)
-  bool w_zeroed = true;  // this iteration's list buffer's counts are zero (initially: the memsets above)
-  for (int outer = 0; outer <= 2 * (D.max_iter + 2); outer++) {
-    int* rd = par[(outer + 1) & 1];  // the list the previous iteration wrote (or the init kernel)
-    dnp = par[outer & 1];
-    dn = dnp + 1;
-    int* zn = rd;  // zeroed by this iteration's finish kernel, for the next iteration
-    // the derivative and sweep launches cover the active instances only (compact list)
-    IlqrDev Dm = D;  // (the mirror: the previous iteration's counts, seq = outer; 0 = none yet)
-    if (hmr && outer > 0) {
-      Dm.mirror = dmr;
-      Dm.mirror_seq = outer;
-    }
-    if ((st = run_backward(ctx, Dm, B, dX, dU, rd + 2, rd + 1, n_act, dk, dK))) return st;
-    if (!w_zeroed) MP_HIP(ctx, hipMemsetAsync(dnp, 0, 2 * sizeof(int), ctx->stream));
-    w_zeroed = false;
-    mp_time_begin(ctx);
-    // The switch to the one-pass search is terminal (once armed it stays, whatever later polls
-    // say).  Instances the last pipelined launch left pending keep their active flag and their
-    // gains (they sat the backward pass out), so the one-pass search reruns them from trial 0:
-    // trials 0..15 give the bits round 0 gave, so they end exactly where their rest pass would.
-    if (rest && (onepass_armed || n_act <= kOnePassMax)) {
-      int *winm1 = dpw + 6 * (size_t)B, *ms1 = dpw + 7 * (size_t)B;
-      if (!onepass_armed) MP_HIP(ctx, hipMemsetAsync(winm1, 0x7f, sizeof(int) * B, ctx->stream));
-      onepass_armed = true;
-      hipLaunchKernelGGL((ilqr_search_rest_kernel<kSearchG, kSearchL>),
-                         dim3((unsigned)B, (unsigned)((T2 + 64 / kSearchL - 1) / (64 / kSearchL))), b1, 0, ctx->stream, D,
-                         B, dX, dU, dk, dK, dJ, dact, ms1, dXs2, dUs2, dJt, winm1, 0, T2);
-      MP_HIP(ctx, hipGetLastError());
-      hipLaunchKernelGGL(ilqr_search_finish_kernel<kSearchG>, dim3((unsigned)B), b1, 0, ctx->stream, D, B, dX, dU, dact,
-                         ms1, dXs2, dUs2, dJt, winm1, dJ, dact, dit, dfl, dn, 0, T2, 2, zn);
-      MP_HIP(ctx, hipGetLastError());
-      w_zeroed = zn != nullptr;
-      mp_time_end(ctx);
-      bool stop;
-      if ((st = poll(outer, &stop))) return st;
-      if (stop) break;
-      continue;
-    }
-    // G = 16: a lane quad per trial (4 waves per SIMD at B = 4096); the narrower fallbacks one lane
-    const int l0 = rest && n_act >= kPairMin ? kRound0L : kSearchL;
-    const int ipw = G == kSearchG ? 64 / (kSearchG * l0) : 64 / G;
-    const dim3 gs((unsigned)((B + ipw - 1) / ipw));
-    if (rest) {
-      const int cur = q2 & 1, old = cur ^ 1;
-      q2++;
-      int *pend_n = dpw + cur * B, *pend_o = dpw + old * B;
-      int* winm_o = dpw + (2 + old) * B;  // pend_n is 0 and winm[cur] 0x7f7f7f7f: reset by the finish
-      int *ms_n = dpw + (4 + cur) * B, *ms_o = dpw + (4 + old) * B;  // kernel that last used them
-      const unsigned ncol = (unsigned)((T2 + 64 / kSearchL - 1) / (64 / kSearchL));
-      auto pipe_k = l0 == kRound0L ? ilqr_search_pipe_kernel<kSearchG, kSearchL, kRound0L>
-                                   : ilqr_search_pipe_kernel<kSearchG, kSearchL, kSearchL>;
-      hipLaunchKernelGGL(pipe_k, dim3(gs.x + (unsigned)B * ncol), b1, 0,
-                         ctx->stream, D, B, dX, dU, dk, dK, dXn, dUn, dJ, dact, dit, dfl, dn, pend_n, ms_n, dnp,
-                         pend_o, ms_o, dXs2, dUs2, dJt, winm_o, T2, (int)gs.x);
-      MP_HIP(ctx, hipGetLastError());
-      hipLaunchKernelGGL(ilqr_search_finish_kernel<kSearchG>, dim3((unsigned)B), b1, 0, ctx->stream, D, B, dX, dU, pend_o,
-                         ms_o, dXs2, dUs2, dJt, winm_o, dJ, dact, dit, dfl, dn, kSearchG, T2, 3, zn);
-      MP_HIP(ctx, hipGetLastError());
-      w_zeroed = zn != nullptr;
-      mp_time_end(ctx);
-      bool stop;
-      if ((st = poll(outer, &stop))) return st;
-      if (stop) break;
-      continue;
-    }
-    // no rest-pass slots: the G-wide kernel runs its rounds to the end
-    if (G == kSearchG)
-      hipLaunchKernelGGL((ilqr_search_kernel<kSearchG, kSearchL>), gs, b1, 0, ctx->stream, D, B, dX, dU, dk, dK, dXn, dUn, dJ, dact,
-                         dit, dfl, dn, 0, nullptr, nullptr);
-    else if (G == 4)
-      hipLaunchKernelGGL(ilqr_search_kernel<4>, gs, b1, 0, ctx->stream, D, B, dX, dU, dk, dK, dXn, dUn, dJ, dact, dit, dfl, dn,
-                         0, nullptr, nullptr);
-    else
-      hipLaunchKernelGGL(ilqr_search_kernel<1>, gs, b1, 0, ctx->stream, D, B, dX, dU, dk, dK, dXn, dUn, dJ, dact, dit, dfl, dn,
-                         0, nullptr, nullptr);
-    MP_HIP(ctx, hipGetLastError());
-    mp_time_end(ctx);
-    bool stop;
-    if ((st = poll(outer, &stop))) return st;
-    if (stop) break;
-  }
-  std::vector<int> hfl(B);
-  if (dev) {  // X / U are already the caller's; J and the iteration counts device to device
-    MP_HIP(ctx, hipMemcpyAsync(J, dJ, sizeof(double) * B, hipMemcpyDeviceToDevice, ctx->stream));
-    MP_HIP(ctx, hipMemcpyAsync(iters, dit, sizeof(int) * B, hipMemcpyDeviceToDevice, ctx->stream));
-  } else {
-    if ((st = mp_download(ctx, X, (const double*)dX, 4 * N * B))) return st;
-    if ((st = mp_download(ctx, U, (const double*)dU, 2 * N * B))) return st;
-    if ((st = mp_download(ctx, J, (const double*)dJ, (size_t)B))) return st;
-    if ((st = mp_download(ctx, iters, (const int*)dit, (size_t)B))) return st;
-  }
-  if ((st = mp_download(ctx, hfl.data(), (const int*)dfl, (size_t)B))) return st;
-  MP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  int any = 0;
-  for (int b = 0; b < B; b++) any |= hfl[b];
-  if (any & 1) return mp_fail(ctx, MP_ERR_NUMERIC, "line search hit max_ls for some instance (the reference would loop forever)");
-  if (any & 2) return mp_fail(ctx, MP_ERR_NUMERIC, "max_iter reached before |dJ/J| <= tol for some instance");
-  return MP_OK;
+  if (int st = ilqr_enter(ctx, p, B, &D, X && U && k && Kg && alpha && Xnew && Unew && Jnew)) return st;
+  return launch_forward(ctx, D, B, X, U, k, Kg, alpha, Xnew, Unew, Jnew);
 }
 
 int mp_ilqr_solve(mp_ctx* ctx, const mp_ilqr_params* p, int32_t B, double* X, double* U, double* J,

@@ -253,6 +253,50 @@ def test_solve_pipelined_search_bitexact(ctx, B, N):
     assert stalled > 0 and int(it.max()) > 10
 
 
+def test_solve_context_reused_across_strategies():
+    """One context, five solves in a row that take different search strategies and shapes, so each finds the
+    workspace, the list buffers and the pinned and mapped count words as the one before left them: 24 x 20
+    (one-pass from the first iteration, with stalling instances), 600 x 21 (more than 512 active: pipelined, then
+    the switch to one-pass with instances pending), 24 x 20 again, the same under a 1 MiB cap after a trim (the
+    16-wide search without rest slots), and 600 x 21 once more with the cap lifted.  Each result -- X, U, J,
+    iteration counts, status -- equals, bit for bit, that of the same solve on a fresh context of its own."""
+    from motionplanning_amd.context import Context
+
+    def problem(B, N, seed):
+        p = ilqr.params(N=N, max_iter=60)
+        x0, U0 = ilqr.cfg3_instances(B, N, seed)
+        return p, x0, U0
+
+    def solve(c, prob, cap=0):
+        p, x0, U0 = prob
+        if cap:
+            c.trim()
+            c.set_workspace_limit(cap)
+        X0, _ = ilqr.ilqr_rollout(p, x0, U0, ctx=c)
+        return ilqr.ilqr_solve(p, X0, U0, ctx=c)
+
+    def fresh(prob, cap=0):
+        c = Context(0)
+        try:
+            return solve(c, prob, cap)
+        finally:
+            c.close()
+
+    small, big = problem(24, 20, 7), problem(600, 21, 11)
+    want_small, want_capped, want_big = fresh(small), fresh(small, 1 << 20), fresh(big)
+    assert int(want_big[3].max()) > 10  # the big solve does stay pipelined for many iterations
+    c = Context(0)
+    try:
+        got = [solve(c, small), solve(c, big), solve(c, small), solve(c, small, 1 << 20)]
+        c.set_workspace_limit(0)
+        got.append(solve(c, big))
+    finally:
+        c.close()
+    for i, (g, w) in enumerate(zip(got, (want_small, want_big, want_small, want_capped, want_big))):
+        for a, b in zip(g, w):
+            assert np.array_equal(a, b, equal_nan=True), i
+
+
 # ------------------------------------------------------------------ knots off the pinv's generic path
 # tests/ilqr_rare_cases.py: at rest (diagonal Quu at every knot), creeping (dbdsqr splits), braking to rest (one
 # sweep crosses from diagonal to generic knots), a NaN state, ax = 80 (the barrier's exp far branch), headings at

@@ -7,7 +7,7 @@ for r in rows:
     n = r['Kernel_Name'].replace('(anonymous namespace)::', '')
     d = (int(r['End_Timestamp']) - int(r['Start_Timestamp'])) / 1e3
     short = n.split('(')[0].split('<')[0].replace('void ', '')
-    if short == 'ilqr_deriv_kernel':
+    if short in ('ilqr_backward_fused_kernel', 'ilqr_deriv4_kernel'):  # an iteration's first kernel (run_backward)
         if cur: out.append(cur)
         cur = {'t0': int(r['Start_Timestamp'])}
     if cur is not None and 'ilqr' in short:
