@@ -731,6 +731,36 @@ int mp_path_collision(mp_ctx* ctx, const mp_collide_params_t* p, int32_t B, int3
                       uint8_t* scene_free, int32_t* first_pose, int32_t* first_wall, int32_t* n_hit,
                       uint8_t* pose_free);
 
+/* ---------------------------------------------------------- Reeds-Shepp curves */
+/* PathPlanning/ReedsSheppsCurves (main.jl, src/ReedsSheppsUtils.jl) for many pose pairs at once.  Poses are
+ * [x, y, ψ]; a command table is [5][3] with rows [length, gear, steer] (Julia's 3x5 matrix), candidates are
+ * numbered 0..47 as allpath numbers them (4*(word - 1) + variant: plain, timeflip, reflect, reverse).
+ * Every value is the reference's in fp64.  Common errors, MP_ERR_INVALID with nothing written: a NULL
+ * argument that is not marked optional, a count below 1.  An output above the context's workspace limit:
+ * MP_ERR_NOMEM. */
+
+/* ReedsSheppsCurves/main.jl:15-17 for B pose pairs: changeBasis on the device, allpath, argmin.
+ * init[B][3], term[B][3], minR[B] (any sign; IEEE results flow through as in mp_ha_allpath).
+ * out: norm[B][3] (NULL: not returned), cost[B][48], cmds[B][48][5][3] (NULL: not returned),
+ *      best[B] (Julia findmin: first NaN, else first minimum), act_cost[B] = cost[best]*minR. */
+int mp_rs_allpath(mp_ctx* ctx, int32_t B, const double* init, const double* term, const double* minR,
+                  double* norm, double* cost, double* cmds, int32_t* best, double* act_cost);
+
+/* createPath / createActPath (ReedsSheppsUtils.jl:411-466) for n command tables cmds[n][5][3]
+ * (rows up to the first with gear == 0 count, later rows are ignored).
+ * init[n][3] and minR[n] both given: createActPath.  Both NULL: createPath (start [0,0,0], no scaling).
+ * One NULL only: MP_ERR_INVALID.
+ * out: path_len[n] = 100*nseg + 1 (1 for an all-zero table: the start alone),
+ *      path[n][501][3]; columns from path_len on are 0.0. */
+int mp_rs_create_path(mp_ctx* ctx, int64_t n, const double* init, const double* minR, const double* cmds,
+                      double* path, int32_t* path_len);
+
+/* The Reeds-Shepp distance (rs_heuristic, hybrid_astar_utils.jl:361-373: opt_cost*minR) from every
+ * a[na][3] to every b[nb][3] at one minR.
+ * out: dist[na][nb]; best[na][nb] (candidate index 0..47; NULL: not returned). */
+int mp_rs_cost_matrix(mp_ctx* ctx, int32_t na, const double* a, int32_t nb, const double* b, double minR,
+                      double* dist, uint8_t* best);
+
 /* ---------------------------------------------------------- diagnostics */
 /* Evaluate one include/mp_jlmath.h function on the device for n inputs
  * (bit-exactness check against the CPU build).  fn: 0 sin, 1 cos, 2 tan, 3 atan,

@@ -31,7 +31,8 @@ using Interpolations: interpolate, Gridded, Constant, Previous, linear_interpola
 export MPPIPlan, MPPIClosedLoop, planHybridAstar!, mppi_plan_batch, mppi_plan_sharded, comm_init, mppi_closed_loop_batch,
        rollout_batch, ha_expand, ha_rs_connect, ha_astar_table, astar_plan_batch, dka_plan_batch, bfs_plan_batch, grid_plan_batch, rrt_plan_batch, rrtnh_plan_batch,
        ha_allpath, ha_neighbor_origin, retrieve_batch!, track_batch!, ilqr_rollout, ilqr_backward!, ilqr_forward!,
-       ilqr_solve!, vehicle_euler!, ctx_join
+       ilqr_solve!, vehicle_euler!, ctx_join, rs_allpath, rs_create_path, rs_cost_matrix, changeBasis, allpath,
+       createPath, createActPath
 
 const libmpgpu = get(ENV, "MPGPU_LIB", joinpath(@__DIR__, "..", "motionplanning_amd", "lib", "libmpgpu.so"))
 
@@ -803,6 +804,88 @@ function ha_allpath(ns::Matrix{Float64})
     check(GC.@preserve ns cost cmds best ccall((:mp_ha_allpath, libmpgpu), Cint,
         (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}), c, B, ns, cost, cmds, best), c)
     return best .+ 1, cost, cmds
+end
+
+# ------------------------------------------------------ Reeds-Shepp curves
+"""
+    rs_allpath(init, term, minR; want_norm = true, want_cmds = true)
+
+ReedsSheppsCurves/main.jl:15-17 for B pose pairs (mp_rs_allpath): init, term (3, B), minR (B).  Returns norm (3, B),
+cost (48, B), cmds (3, 5, 48, B) (rows [length, gear, steer] of each command; `nothing` when not wanted), best
+(1-based) and act_cost = cost[best] * minR.
+"""
+function rs_allpath(init::Matrix{Float64}, term::Matrix{Float64}, minR::Vector{Float64}; want_norm = true,
+                    want_cmds = true)
+    B = size(init, 2)
+    norm = zeros(3, want_norm ? B : 0); cost = zeros(48, B); cmds = zeros(3, 5, 48, want_cmds ? B : 0)
+    best = zeros(Int32, B); act = zeros(B)
+    c = ctx()
+    check(GC.@preserve init term minR norm cost cmds best act ccall((:mp_rs_allpath, libmpgpu), Cint,
+        (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Ptr{Int32}, Ptr{Float64}),
+        c, B, init, term, minR, want_norm ? pointer(norm) : C_NULL, cost, want_cmds ? pointer(cmds) : C_NULL, best,
+        act), c)
+    return (; norm = want_norm ? norm : nothing, cost, cmds = want_cmds ? cmds : nothing, best = best .+ 1,
+            act_cost = act)
+end
+
+"""
+    rs_create_path(cmds; init = nothing, minR = nothing)
+
+createPath / createActPath (ReedsSheppsUtils.jl:411-466) for n command tables cmds (3, 5, n) (mp_rs_create_path);
+init (3, n) and minR (n) both given: createActPath, neither: createPath.  Returns path (3, 501, n), zero from column
+path_len[i] + 1 on, and path_len (n).
+"""
+function rs_create_path(cmds::Array{Float64,3}; init = nothing, minR = nothing)
+    n = size(cmds, 3)
+    i0 = init === nothing ? Float64[] : Matrix{Float64}(init)
+    mr = minR === nothing ? Float64[] : Vector{Float64}(minR)
+    path = zeros(3, 501, n); plen = zeros(Int32, n)
+    c = ctx()
+    check(GC.@preserve cmds i0 mr path plen ccall((:mp_rs_create_path, libmpgpu), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+        c, n, init === nothing ? C_NULL : pointer(i0), minR === nothing ? C_NULL : pointer(mr), cmds, path, plen), c)
+    return path, plen
+end
+
+"""The Reeds-Shepp distance opt_cost * minR (rs_heuristic, hybrid_astar_utils.jl:361-373) from every a (3, na) to
+every b (3, nb) (mp_rs_cost_matrix): dist (nb, na) and the winning candidates best (nb, na), 1-based."""
+function rs_cost_matrix(a::Matrix{Float64}, b::Matrix{Float64}, minR::Float64)
+    na = size(a, 2); nb = size(b, 2)
+    dist = zeros(nb, na); best = zeros(UInt8, nb, na)
+    c = ctx()
+    check(GC.@preserve a b dist best ccall((:mp_rs_cost_matrix, libmpgpu), Cint,
+        (Ptr{Cvoid}, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Float64, Ptr{Float64}, Ptr{UInt8}),
+        c, na, a, nb, b, minR, dist, best), c)
+    return dist, best .+ 0x01
+end
+
+# the reference's names and shapes (ReedsSheppsUtils.jl); a command table is 5 x 3, a path 3 x n
+changeBasis(init_st, termi_st, minR) =
+    vec(rs_allpath(reshape(Vector{Float64}(init_st), 3, 1), reshape(Vector{Float64}(termi_st), 3, 1),
+                   [Float64(minR)]; want_cmds = false).norm)
+
+function allpath(states)
+    best, cost, cmds = ha_allpath(reshape(Vector{Float64}(states), 3, 1))
+    res_cmds = permutedims(cmds[:, :, :, 1], (2, 1, 3))    # (3, 5, 48) -> 5 x 3 x 48
+    return res_cmds[:, :, best[1]], cost[best[1], 1], res_cmds, cost[:, 1]
+end
+
+function _rs_table(cmds)
+    t = zeros(3, 5, 1)
+    t[:, 1:size(cmds, 1), 1] = permutedims(Matrix{Float64}(cmds))
+    return t
+end
+
+function createPath(cmds)
+    path, plen = rs_create_path(_rs_table(cmds))
+    return path[:, 1:plen[1], 1]
+end
+
+function createActPath(init_st, minR, cmds)
+    path, plen = rs_create_path(_rs_table(cmds); init = reshape(Vector{Float64}(vec(init_st)), 3, 1),
+                                minR = [Float64(minR)])
+    return path[:, 1:plen[1], 1]
 end
 
 # ------------------------------------------------------ collision detection

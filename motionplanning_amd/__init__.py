@@ -1,1 +1,2 @@
 from . import collision  # noqa: F401
+from . import reeds_shepp  # noqa: F401

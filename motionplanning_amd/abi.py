@@ -227,6 +227,9 @@ SIGNATURES = {
     "mp_block_pts": (ctypes.c_int, [_V, ctypes.c_int64, _V, _V]),
     "mp_convex_collision": (ctypes.c_int, [_V, _I, _I, _I, _I, _V, _V, _I, _I, _V, _V, _V]),
     "mp_path_collision": (ctypes.c_int, [_V, ctypes.POINTER(CollideParams), _I, _I, _V, _V, _I] + [_V] * 7),
+    "mp_rs_allpath": (ctypes.c_int, [_V, _I] + [_V] * 8),
+    "mp_rs_create_path": (ctypes.c_int, [_V, ctypes.c_int64] + [_V] * 5),
+    "mp_rs_cost_matrix": (ctypes.c_int, [_V, _I, _V, _I, _V, ctypes.c_double, _V, _V]),
     "mp_math_eval": (ctypes.c_int, [_V, _I, ctypes.c_int64, _V, _V, _V]),
     "mp_pinv2_eval": (ctypes.c_int, [_V, _I, ctypes.c_int64, _V, _V, _V]),
     "mp_comm_init": (ctypes.c_int, [_V, _I]),
