@@ -500,13 +500,19 @@ constexpr int HA_NGR = 16;
 // and fail the plan (Q.err), not read another iteration's node
 constexpr int HA_NGR_SLOTS = 8;
 constexpr unsigned HA_NGR_DONE = 0xffffffffu;
+// A node as popfirst! hands it on (an open entry without its key), ten words: node id, g (bits), Encode index,
+// state (3, bits), rs_heuristic's stored winner word, the winner's (t, u, v) (3, bits).  The bookkeeping's staging
+// arrays, the prescan record's entries and the granule writer below index it by these names
+enum { NP_ID = 0, NP_G, NP_IX, NP_ST, NP_RW = NP_ST + 3, NP_TUV, NP_N = NP_TUV + 3 };
+static_assert(NP_N == 10 && 2 * (NP_RW - NP_ST) + 2 * (NP_N - NP_TUV) + 2 == 14,
+              "the granules: the halves of the state and of (t, u, v), the winner word, the go word");
 __device__ __forceinline__ void ha_publish_node(unsigned long long* g, unsigned tag, int lane, const long long* w,
                                                 unsigned go) {
   if (lane >= 14) return;
   unsigned v;
-  if (lane < 6) v = (unsigned)((unsigned long long)w[3 + (lane >> 1)] >> (32 * (lane & 1)));  // state
-  else if (lane < 12) v = (unsigned)((unsigned long long)w[7 + ((lane - 6) >> 1)] >> (32 * (lane & 1)));  // tuv
-  else if (lane == 12) v = (unsigned)(int)w[6];  // rs winner word
+  if (lane < 6) v = (unsigned)((unsigned long long)w[NP_ST + (lane >> 1)] >> (32 * (lane & 1)));  // state
+  else if (lane < 12) v = (unsigned)((unsigned long long)w[NP_TUV + ((lane - 6) >> 1)] >> (32 * (lane & 1)));  // tuv
+  else if (lane == 12) v = (unsigned)(int)w[NP_RW];  // rs winner word
   else v = go;
   __hip_atomic_store(g + lane, ((unsigned long long)tag << 32) | v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -1353,14 +1359,15 @@ struct HaSearch {
   double* otuv;          // [B][C][3] open entries: the same
   double* node_tuv;      // [2][B][3] popped node's, double-buffered like node
   long long* pre;        // [B][PRE_W] (RSH tail) the prescan's record: popfirst!'s K least entries before FindNewNode
-  unsigned long long* ngr;  // [HA_NGR_SLOTS][B][HA_NGR] the popped node as tagged granules (ha_publish_node), by it & 3
+  unsigned long long* ngr;  // [HA_NGR_SLOTS][B][HA_NGR] the popped node as tagged granules (ha_publish_node), by
+                            // it & (HA_NGR_SLOTS - 1)
   int* nx;               // [B] (ha_pipe_kernel) 2·it + 2 + go once iteration it's bookkeeping has popped the next node
   int* ex;               // [B] (ha_persist_kernel) expansions finished (neighbour groups, cumulative)
   int* rsr;              // [2][B] (ha_persist_kernel) 2·it + 2 once RS_connected(n_it) has run, by it & 1 (its RS block)
   int* err;              // [1] (ha_persist_kernel) a bounded wait ran out (the search is then not trusted)
   // (ha_persist_kernel, SPEC) the runner-up: popfirst!'s second-least entry when n_{it+1} is popped, the
   // candidate for n_{it+2}, expanded (and RS_connected) speculatively
-  unsigned long long* ngr2;  // [HA_NGR_SLOTS][B][HA_NGR] the runner-up as tagged granules, by it & 3
+  unsigned long long* ngr2;  // [HA_NGR_SLOTS][B][HA_NGR] the runner-up as tagged granules, by it & (HA_NGR_SLOTS - 1)
   int* exs;              // [2][B] speculative expansions finished (neighbour groups, cumulative), by the parity of the runner-up's iteration
   int* rsrs;             // [2][B] 2·it + 2 once RS_connected(r_it) has run, by it & 1
   int* nhit;             // [2][B] (diagnostics) pops that were the runner-up, runner-ups published
@@ -1385,8 +1392,10 @@ __device__ __forceinline__ double astar_h(const HaDev& P, const HaSearch& Q, int
   return tab[(size_t)b * 121 + (cy - 1) * 11 + (cx - 1)];
 }
 // prescan record: [0] iteration tag, [1] kc = min(K, n_open), then K entries of 13 words: f (bits), seq, position,
-// node id, g (bits), Encode index, state (3, bits), rw, (t, u, v) (3, bits)
+// and the entry's payload (NP_*)
 constexpr int PRE_K = 4, PRE_E = 13, PRE_W = 2 + PRE_E * PRE_K;
+enum { PRE_F = 0, PRE_SEQ, PRE_POS, PRE_PAY };
+static_assert(PRE_E == PRE_PAY + NP_N, "a record entry: (f, seq, pos) and the payload");
 enum { SI_NNODES = 0, SI_NOPEN, SI_LOOP, SI_CUR, SI_ACTIVE, SI_FOUND, SI_NSTATES, SI_RSLEN, SI_N };
 
 // open-list order: a before c (Julia isless on f, then list position)
@@ -1421,6 +1430,61 @@ __device__ __forceinline__ void key_min_dpp(double& f, long long& sq, int& p) {
     sq = os;
     p = op;
   }
+}
+// the row minimum: quad xor 1 / xor 2, then the half-row and row mirrors; every lane then holds the least of its
+// row of 16 lanes
+__device__ __forceinline__ void key_min_row(double& f, long long& sq, int& p) {
+  key_min_dpp<0xB1>(f, sq, p);
+  key_min_dpp<0x4E>(f, sq, p);
+  key_min_dpp<0x141>(f, sq, p);
+  key_min_dpp<0x140>(f, sq, p);
+}
+// the wave minimum: the row steps (spelt out: calling key_min_row here cost ha_init_kernel two VGPRs), then the four
+// rows by v_readlane; every lane then holds the (wave-uniform) winner
+__device__ __forceinline__ void key_min_wave(double& f, long long& sq, int& p) {
+  key_min_dpp<0xB1>(f, sq, p);
+  key_min_dpp<0x4E>(f, sq, p);
+  key_min_dpp<0x141>(f, sq, p);
+  key_min_dpp<0x140>(f, sq, p);
+  double wf = __longlong_as_double(readlane_l(__double_as_longlong(f), 0));
+  long long ws = readlane_l(sq, 0);
+  int wp = __builtin_amdgcn_readlane(p, 0);
+#pragma unroll
+  for (int r = 1; r < 4; r++) {
+    const double of = __longlong_as_double(readlane_l(__double_as_longlong(f), 16 * r));
+    const long long os = readlane_l(sq, 16 * r);
+    const int op = __builtin_amdgcn_readlane(p, 16 * r);
+    if (op >= 0 && (wp < 0 || key_before(of, os, wf, ws))) { wf = of; ws = os; wp = op; }
+  }
+  f = wf;
+  sq = ws;
+  p = wp;
+}
+
+// the payload (y[NP_N]) of open entry q = the scene's base + position
+__device__ __forceinline__ void ha_entry_pay(const HaSearch& Q, size_t q, long long* y) {
+  y[NP_ID] = Q.oid[q];
+  y[NP_G] = __double_as_longlong(Q.og[q]);
+  y[NP_IX] = Q.oix[q];
+#pragma unroll
+  for (int e = 0; e < 3; e++) y[NP_ST + e] = __double_as_longlong(Q.ost[q * 3 + e]);
+  y[NP_RW] = Q.orw[q];
+#pragma unroll
+  for (int e = 0; e < 3; e++) y[NP_TUV + e] = __double_as_longlong(Q.otuv[q * 3 + e]);
+}
+// the payload of the entry a lane's FindNewNode decision changes or appends
+__device__ __forceinline__ void ha_lane_pay(long long* y, int id, double g, long long ix, double s0, double s1,
+                                            double s2, int rw, double t0, double t1, double t2) {
+  y[NP_ID] = id;
+  y[NP_G] = __double_as_longlong(g);
+  y[NP_IX] = ix;
+  y[NP_ST] = __double_as_longlong(s0);
+  y[NP_ST + 1] = __double_as_longlong(s1);
+  y[NP_ST + 2] = __double_as_longlong(s2);
+  y[NP_RW] = rw;
+  y[NP_TUV] = __double_as_longlong(t0);
+  y[NP_TUV + 1] = __double_as_longlong(t1);
+  y[NP_TUV + 2] = __double_as_longlong(t2);
 }
 
 // popfirst! for scene b (an NT-thread block): the least (f, seq) open entry, found by a
@@ -1506,26 +1570,7 @@ __device__ __forceinline__ bool ha_pop(const HaSearch& Q, int B, int b, int n_op
     __hip_atomic_store(stp + 10, __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   const int own = bp;
-  // wave minimum: quad xor 1 / xor 2, half-row and row mirrors, then the four rows by v_readlane
-  key_min_dpp<0xB1>(bf, bs, bp);
-  key_min_dpp<0x4E>(bf, bs, bp);
-  key_min_dpp<0x141>(bf, bs, bp);
-  key_min_dpp<0x140>(bf, bs, bp);
-  {
-    double wf = __longlong_as_double(readlane_l(__double_as_longlong(bf), 0));
-    long long ws = readlane_l(bs, 0);
-    int wp_ = __builtin_amdgcn_readlane(bp, 0);
-#pragma unroll
-    for (int r = 1; r < 4; r++) {
-      const double of_ = __longlong_as_double(readlane_l(__double_as_longlong(bf), 16 * r));
-      const long long os = readlane_l(bs, 16 * r);
-      const int op = __builtin_amdgcn_readlane(bp, 16 * r);
-      if (op >= 0 && (wp_ < 0 || key_before(of_, os, wf, ws))) { wf = of_; ws = os; wp_ = op; }
-    }
-    bf = wf;
-    bs = ws;
-    bp = wp_;
-  }
+  key_min_wave(bf, bs, bp);
   if (lane == 0) { r_f[wave] = bf; r_s[wave] = bs; r_p[wave] = bp; }
   if (bp >= 0 && own == bp) {  // the one lane that scanned the wave's winning position
     r_id[wave] = pid;
@@ -1558,10 +1603,7 @@ __device__ __forceinline__ bool ha_pop(const HaSearch& Q, int B, int b, int n_op
     cs = r_s[lane];
   }
   const int mine = cp;
-  key_min_dpp<0xB1>(cf, cs, cp);
-  key_min_dpp<0x4E>(cf, cs, cp);
-  key_min_dpp<0x141>(cf, cs, cp);
-  key_min_dpp<0x140>(cf, cs, cp);
+  key_min_row(cf, cs, cp);
   bp = __builtin_amdgcn_readlane(cp, 0);
   const int ww = __builtin_ctzll(__ballot(lane < NT / 64 && mine == bp));
   const int id = r_id[ww];
@@ -1663,6 +1705,31 @@ struct BookRec {
   long long v[RC_N];
 };
 
+// duplicates: lane k of wave 0 is neighbour k; an earlier valid lane with the same Encode index makes it one.
+// Only the first valid occurrence of an Encode index in this expansion can change anything (every neighbour has
+// the same tentative g).  The 64 comparisons per lane are split over four waves (wave w: earlier lanes
+// 16w..16w+15, broadcast LDS reads, unconditional: no exec-masked branch per j).  vix, dup: the caller's LDS;
+// the verdicts (ha_is_dup) are complete after the caller's next __syncthreads
+__device__ __forceinline__ void ha_dup_check(int tid, bool valid, long long ix, long long* vix, int (*dup)[64]) {
+  const int lane = tid & 63;
+  if (tid < 64) vix[tid] = valid ? ix : 0;
+  __syncthreads();
+  if (tid < 256) {
+    const int w = tid >> 6;
+    const long long key = vix[lane];
+    bool d = false;
+#pragma unroll
+    for (int jj = 0; jj < 16; jj++) {
+      const int j = 16 * w + jj;
+      const long long oj = vix[j];
+      d = d | ((oj == key) & (j < lane) & (key != 0));
+    }
+    dup[w][lane] = d;
+  }
+}
+__device__ __forceinline__ bool ha_is_dup(const int (*dup)[64], int k) {
+  return dup[0][k] | dup[1][k] | dup[2][k] | dup[3][k];
+}
 // FindNewNode's Dict / open-list updates (:418-446) on wave 0 (neighbour k on lane k) + the next popfirst!
 // (whole block) for scene b on an NT-thread block: the neighbour records are read agent-coherently; the node
 // count, the pop count and pop_seq go to the scene's record (Q.rec) for the finisher (ha_finish, which also
@@ -1735,37 +1802,22 @@ __device__ __forceinline__ BookRec ha_book_spec(const HaDev& P, const HaSearch& 
     if (n_open0 > 0 && lane < PRE_E) {
       const size_t L = base + n_open0 - 1;
       switch (lane) {
-        case 0: lastw = __double_as_longlong(Q.of[L]); break;
-        case 1: lastw = Q.oseq[L]; break;
-        case 2: lastw = L - base; break;
-        case 3: lastw = Q.oid[L]; break;
-        case 4: lastw = __double_as_longlong(Q.og[L]); break;
-        case 5: lastw = Q.oix[L]; break;
-        case 6: case 7: case 8: lastw = __double_as_longlong(Q.ost[L * 3 + lane - 6]); break;
-        case 9: lastw = Q.orw[L]; break;
-        default: lastw = __double_as_longlong(Q.otuv[L * 3 + lane - 10]); break;
+        case PRE_F: lastw = __double_as_longlong(Q.of[L]); break;
+        case PRE_SEQ: lastw = Q.oseq[L]; break;
+        case PRE_POS: lastw = L - base; break;
+        case PRE_PAY + NP_ID: lastw = Q.oid[L]; break;
+        case PRE_PAY + NP_G: lastw = __double_as_longlong(Q.og[L]); break;
+        case PRE_PAY + NP_IX: lastw = Q.oix[L]; break;
+        case PRE_PAY + NP_ST: case PRE_PAY + NP_ST + 1: case PRE_PAY + NP_ST + 2:
+          lastw = __double_as_longlong(Q.ost[L * 3 + lane - (PRE_PAY + NP_ST)]);
+          break;
+        case PRE_PAY + NP_RW: lastw = Q.orw[L]; break;
+        default: lastw = __double_as_longlong(Q.otuv[L * 3 + lane - (PRE_PAY + NP_TUV)]); break;
       }
     }
   }
-  // duplicates: lane k of wave 0 is neighbour k; an earlier valid lane with the same Encode index makes
-  // it one.  Only the first valid occurrence of an Encode index in this expansion can change anything (every
-  // neighbour has the same tentative g).  The 64 comparisons per lane are split over four waves (wave w: earlier
-  // lanes 16w..16w+15, broadcast LDS reads, unconditional: no exec-masked branch per j)
   const bool valid = tid < np && ix != 0 && frk;
-  if (tid < 64) s_vix[tid] = valid ? ix : 0;
-  __syncthreads();
-  if (tid < 256) {
-    const int w = tid >> 6;
-    const long long key = s_vix[lane];
-    bool d = false;
-#pragma unroll
-    for (int jj = 0; jj < 16; jj++) {
-      const int j = 16 * w + jj;
-      const long long oj = s_vix[j];
-      d = d | ((oj == key) & (j < lane) & (key != 0));
-    }
-    s_dup[w][lane] = d;
-  }
+  ha_dup_check(tid, valid, ix, s_vix, s_dup);
   int hit = -1;
   double gd = 0.0, fo_ = 0.0, dst0 = 0.0, dst1 = 0.0, dst2 = 0.0;
   int po = 0, drw = -1;
@@ -1792,7 +1844,7 @@ __device__ __forceinline__ BookRec ha_book_spec(const HaDev& P, const HaSearch& 
   if (tid < 64) {
     int n_open = n_open0;
     const int k = lane;
-    const bool dup = s_dup[0][k] | s_dup[1][k] | s_dup[2][k] | s_dup[3][k];
+    const bool dup = ha_is_dup(s_dup, k);
     const bool first = valid && !dup;
     const double tg = cur_g + P.expand_time;
     double th = 0.0, tf = 0.0;
@@ -1902,7 +1954,6 @@ __device__ __forceinline__ BookRec ha_book_spec(const HaDev& P, const HaSearch& 
       double bf = tf;
       long long bs = nseq;
       int bp = myp;
-      int bl = myp >= 0 ? lane : -1;  // the lane holding the winner (-1: a record entry)
       // the record's entries FindNewNode left alone (wave-uniform)
       bool any_left = false;
       double rf = 0.0;
@@ -1911,10 +1962,10 @@ __device__ __forceinline__ BookRec ha_book_spec(const HaDev& P, const HaSearch& 
 #pragma unroll
       for (int e = 0; e < PRE_K; e++) {
         if (e >= kc) break;
-        const int pe = (int)readlane_l(recw, 2 + PRE_E * e + 2);
+        const int pe = (int)readlane_l(recw, 2 + PRE_E * e + PRE_POS);
         if (__ballot(chg && po == pe)) continue;  // changed in place: its new key is a lane candidate
-        const double fe = __longlong_as_double(readlane_l(recw, 2 + PRE_E * e));
-        const long long se = readlane_l(recw, 2 + PRE_E * e + 1);
+        const double fe = __longlong_as_double(readlane_l(recw, 2 + PRE_E * e + PRE_F));
+        const long long se = readlane_l(recw, 2 + PRE_E * e + PRE_SEQ);
         any_left = true;
         if (rp < 0 || key_before(fe, se, rf, rsq)) { rf = fe; rsq = se; rp = pe; re = e; }
       }
@@ -1922,20 +1973,10 @@ __device__ __forceinline__ BookRec ha_book_spec(const HaDev& P, const HaSearch& 
       if (ok_merge) {
         // the lanes' minimum
         int bpl = bp;
-        key_min_dpp<0xB1>(bf, bs, bpl);
-        key_min_dpp<0x4E>(bf, bs, bpl);
-        key_min_dpp<0x141>(bf, bs, bpl);
-        key_min_dpp<0x140>(bf, bs, bpl);
-        double wf = __longlong_as_double(readlane_l(__double_as_longlong(bf), 0));
-        long long ws = readlane_l(bs, 0);
-        int wpos = __builtin_amdgcn_readlane(bpl, 0);
-#pragma unroll
-        for (int q = 1; q < 4; q++) {
-          const double of_ = __longlong_as_double(readlane_l(__double_as_longlong(bf), 16 * q));
-          const long long os = readlane_l(bs, 16 * q);
-          const int op = __builtin_amdgcn_readlane(bpl, 16 * q);
-          if (op >= 0 && (wpos < 0 || key_before(of_, os, wf, ws))) { wf = of_; ws = os; wpos = op; }
-        }
+        key_min_wave(bf, bs, bpl);
+        double wf = bf;
+        long long ws = bs;
+        int wpos = bpl;
         // vs the record's least untouched entry
         bool from_rec = false;
         if (rp >= 0 && (wpos < 0 || key_before(rf, rsq, wf, ws))) { wpos = rp; from_rec = true; }
@@ -1946,17 +1987,17 @@ __device__ __forceinline__ BookRec ha_book_spec(const HaDev& P, const HaSearch& 
           double wg, ws0, ws1, ws2, wt0, wt1, wt2;
           long long wix;
           if (from_rec) {
-            const int o = 2 + PRE_E * re;
-            wid = (int)readlane_l(recw, o + 3);
-            wg = __longlong_as_double(readlane_l(recw, o + 4));
-            wix = readlane_l(recw, o + 5);
-            ws0 = __longlong_as_double(readlane_l(recw, o + 6));
-            ws1 = __longlong_as_double(readlane_l(recw, o + 7));
-            ws2 = __longlong_as_double(readlane_l(recw, o + 8));
-            wrw = (int)readlane_l(recw, o + 9);
-            wt0 = __longlong_as_double(readlane_l(recw, o + 10));
-            wt1 = __longlong_as_double(readlane_l(recw, o + 11));
-            wt2 = __longlong_as_double(readlane_l(recw, o + 12));
+            const int o = 2 + PRE_E * re + PRE_PAY;
+            wid = (int)readlane_l(recw, o + NP_ID);
+            wg = __longlong_as_double(readlane_l(recw, o + NP_G));
+            wix = readlane_l(recw, o + NP_IX);
+            ws0 = __longlong_as_double(readlane_l(recw, o + NP_ST));
+            ws1 = __longlong_as_double(readlane_l(recw, o + NP_ST + 1));
+            ws2 = __longlong_as_double(readlane_l(recw, o + NP_ST + 2));
+            wrw = (int)readlane_l(recw, o + NP_RW);
+            wt0 = __longlong_as_double(readlane_l(recw, o + NP_TUV));
+            wt1 = __longlong_as_double(readlane_l(recw, o + NP_TUV + 1));
+            wt2 = __longlong_as_double(readlane_l(recw, o + NP_TUV + 2));
           } else {
             const int wl = __builtin_ctzll(__ballot(myp == wpos && myp >= 0));
             wid = __builtin_amdgcn_readlane(id, wl);
@@ -1994,18 +2035,18 @@ __device__ __forceinline__ BookRec ha_book_spec(const HaDev& P, const HaSearch& 
               lt1 = __longlong_as_double(readlane_l(__double_as_longlong(nt1), hl));
               lt2 = __longlong_as_double(readlane_l(__double_as_longlong(nt2), hl));
             } else {  // the old last entry, untouched by FindNewNode (loaded at the start)
-              lf = __longlong_as_double(readlane_l(lastw, 0));
-              ls = readlane_l(lastw, 1);
-              lid = (int)readlane_l(lastw, 3);
-              lg = __longlong_as_double(readlane_l(lastw, 4));
-              lix = readlane_l(lastw, 5);
-              l0 = __longlong_as_double(readlane_l(lastw, 6));
-              l1 = __longlong_as_double(readlane_l(lastw, 7));
-              l2 = __longlong_as_double(readlane_l(lastw, 8));
-              lrw = (int)readlane_l(lastw, 9);
-              lt0 = __longlong_as_double(readlane_l(lastw, 10));
-              lt1 = __longlong_as_double(readlane_l(lastw, 11));
-              lt2 = __longlong_as_double(readlane_l(lastw, 12));
+              lf = __longlong_as_double(readlane_l(lastw, PRE_F));
+              ls = readlane_l(lastw, PRE_SEQ);
+              lid = (int)readlane_l(lastw, PRE_PAY + NP_ID);
+              lg = __longlong_as_double(readlane_l(lastw, PRE_PAY + NP_G));
+              lix = readlane_l(lastw, PRE_PAY + NP_IX);
+              l0 = __longlong_as_double(readlane_l(lastw, PRE_PAY + NP_ST));
+              l1 = __longlong_as_double(readlane_l(lastw, PRE_PAY + NP_ST + 1));
+              l2 = __longlong_as_double(readlane_l(lastw, PRE_PAY + NP_ST + 2));
+              lrw = (int)readlane_l(lastw, PRE_PAY + NP_RW);
+              lt0 = __longlong_as_double(readlane_l(lastw, PRE_PAY + NP_TUV));
+              lt1 = __longlong_as_double(readlane_l(lastw, PRE_PAY + NP_TUV + 1));
+              lt2 = __longlong_as_double(readlane_l(lastw, PRE_PAY + NP_TUV + 2));
             }
             if (lane == 0) {
               Q.of[base + wpos] = lf;
@@ -2176,23 +2217,10 @@ __device__ __forceinline__ bool ha_prescan(const HaSearch& Q, const IterArgs& A,
   // the wave's PRE_K least: PRE_K rounds of the minimum of the lanes' heads, the owner lane shifting its list
 #pragma unroll 1
   for (int r = 0; r < PRE_K; r++) {
-    double bf = tf[0];
-    long long bs = ts[0];
-    int bp = tp[0];
-    key_min_dpp<0xB1>(bf, bs, bp);
-    key_min_dpp<0x4E>(bf, bs, bp);
-    key_min_dpp<0x141>(bf, bs, bp);
-    key_min_dpp<0x140>(bf, bs, bp);
-    double wf = __longlong_as_double(readlane_l(__double_as_longlong(bf), 0));
-    long long ws = readlane_l(bs, 0);
-    int wp_ = __builtin_amdgcn_readlane(bp, 0);
-#pragma unroll
-    for (int q = 1; q < 4; q++) {
-      const double of_ = __longlong_as_double(readlane_l(__double_as_longlong(bf), 16 * q));
-      const long long os = readlane_l(bs, 16 * q);
-      const int op = __builtin_amdgcn_readlane(bp, 16 * q);
-      if (op >= 0 && (wp_ < 0 || key_before(of_, os, wf, ws))) { wf = of_; ws = os; wp_ = op; }
-    }
+    double wf = tf[0];
+    long long ws = ts[0];
+    int wp_ = tp[0];
+    key_min_wave(wf, ws, wp_);
     if (lane == 0) { c_f[wave][r] = wf; c_s[wave][r] = ws; c_p[wave][r] = wp_; }
     if (wp_ >= 0 && tp[0] == wp_) {  // the owner lane drops its head
 #pragma unroll
@@ -2215,23 +2243,10 @@ __device__ __forceinline__ bool ha_prescan(const HaSearch& Q, const IterArgs& A,
   int mine = -1;  // lane e < kc: the e-th least entry's position
 #pragma unroll 1
   for (int r = 0; r < PRE_K; r++) {
-    double bf = cf;
-    long long bs = cs;
-    int bp = cp;
-    key_min_dpp<0xB1>(bf, bs, bp);
-    key_min_dpp<0x4E>(bf, bs, bp);
-    key_min_dpp<0x141>(bf, bs, bp);
-    key_min_dpp<0x140>(bf, bs, bp);
-    double wf = __longlong_as_double(readlane_l(__double_as_longlong(bf), 0));
-    long long ws = readlane_l(bs, 0);
-    int wp_ = __builtin_amdgcn_readlane(bp, 0);
-#pragma unroll
-    for (int q = 1; q < 4; q++) {
-      const double of_ = __longlong_as_double(readlane_l(__double_as_longlong(bf), 16 * q));
-      const long long os = readlane_l(bs, 16 * q);
-      const int op = __builtin_amdgcn_readlane(bp, 16 * q);
-      if (op >= 0 && (wp_ < 0 || key_before(of_, os, wf, ws))) { wf = of_; ws = os; wp_ = op; }
-    }
+    double wf = cf;
+    long long ws = cs;
+    int wp_ = cp;
+    key_min_wave(wf, ws, wp_);
     if (lane == r) mine = wp_;
     if (wp_ >= 0 && cp == wp_) { cf = __builtin_inf(); cs = 0x7fffffffffffffffLL; cp = -1; }
   }
@@ -2241,17 +2256,10 @@ __device__ __forceinline__ bool ha_prescan(const HaSearch& Q, const IterArgs& A,
   if (lane < kc && mine >= 0) {  // lane e: entry e and its payload
     const size_t q = base + mine;
     long long w[PRE_E];
-    w[0] = __double_as_longlong(Q.of[q]);
-    w[1] = Q.oseq[q];
-    w[2] = mine;
-    w[3] = Q.oid[q];
-    w[4] = __double_as_longlong(Q.og[q]);
-    w[5] = Q.oix[q];
-#pragma unroll
-    for (int e = 0; e < 3; e++) w[6 + e] = __double_as_longlong(Q.ost[q * 3 + e]);
-    w[9] = Q.orw[q];
-#pragma unroll
-    for (int e = 0; e < 3; e++) w[10 + e] = __double_as_longlong(Q.otuv[q * 3 + e]);
+    w[PRE_F] = __double_as_longlong(Q.of[q]);
+    w[PRE_SEQ] = Q.oseq[q];
+    w[PRE_POS] = mine;
+    ha_entry_pay(Q, q, w + PRE_PAY);
 #pragma unroll
     for (int e = 0; e < PRE_E; e++) st_ag(rec + 2 + PRE_E * lane + e, w[e]);
   }
@@ -2299,7 +2307,7 @@ __device__ __forceinline__ IterArgs e_par(const IterArgs& A, int B, int np, int 
 // SPEC (ha_persist_kernel, SPEC): also the runner-up -- the second-least of popfirst!'s candidates, which is
 // the next pop unless one of the popped node's children beats it (87 % of the pops of configs[3]) -- published
 // as Q.ngr2 granules after the writes; sr (LDS, kept by the caller across iterations) holds the previous one
-// (10 payload words + valid), and the pop's go word carries skip = hit (the popped node IS the previous
+// (the NP_N payload words + valid), and the pop's go word carries skip = hit (the popped node IS the previous
 // runner-up, identical id, state and stored commands: its expansion and RS_connected were made speculatively);
 // *hit_out returns it.
 struct NoWait {
@@ -2318,13 +2326,14 @@ __device__ __forceinline__ BookRec ha_book_pipe(const HaDev& P, const HaSearch& 
   __shared__ double r_f[NT / 64];
   __shared__ long long r_s[NT / 64];
   __shared__ int r_p[NT / 64];
-  __shared__ long long r_pay[NT / 64][11];  // each wave winner's payload: id, g, ix, st[3], rw, tuv[3]
-  __shared__ long long s_win[12];           // the pop's winner: payload as r_pay, position, (SPEC) hit
+  enum { WIN_POS = NP_N, WIN_HIT, WIN_N };
+  __shared__ long long r_pay[NT / 64][NP_N + 1];  // each wave winner's payload (NP_*; one spare word)
+  __shared__ long long s_win[WIN_N];              // the pop's winner: its payload, position, (SPEC) hit
   // (SPEC) the runner-up: each wave's candidate and its payload (staged by the candidate's owner thread)
   __shared__ double u_f[SPEC ? NT / 64 : 1];
   __shared__ long long u_s[SPEC ? NT / 64 : 1];
   __shared__ int u_p[SPEC ? NT / 64 : 1];
-  __shared__ long long u_pay[SPEC ? NT / 64 : 1][10];
+  __shared__ long long u_pay[SPEC ? NT / 64 : 1][NP_N];
   static_assert(NT >= 256 && NT / 64 <= 16, "four waves for the duplicate check, the wave winners fit a row");
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const size_t base = (size_t)b * Q.C;
@@ -2386,20 +2395,7 @@ __device__ __forceinline__ BookRec ha_book_pipe(const HaDev& P, const HaSearch& 
     nb2 = ld_ag(E.nb + 3 * q + 2);
   }
   const bool valid = tid < np && ix != 0 && frk;
-  if (tid < 64) s_vix[tid] = valid ? ix : 0;
-  __syncthreads();
-  if (tid < 256) {
-    const int w = tid >> 6;
-    const long long key = s_vix[lane];
-    bool d = false;
-#pragma unroll
-    for (int jj = 0; jj < 16; jj++) {
-      const int j = 16 * w + jj;
-      const long long oj = s_vix[j];
-      d = d | ((oj == key) & (j < lane) & (key != 0));
-    }
-    s_dup[w][lane] = d;
-  }
+  ha_dup_check(tid, valid, ix, s_vix, s_dup);
   int hit = -1;
   double gd = 0.0, fo_ = 0.0, dst0 = 0.0, dst1 = 0.0, dst2 = 0.0;
   int po = 0, drw = -1;
@@ -2436,7 +2432,7 @@ __device__ __forceinline__ BookRec ha_book_pipe(const HaDev& P, const HaSearch& 
   int n_app = 0, n_open = n_open0;
   if (tid < 64) {
     const int k = lane;
-    const bool dup = s_dup[0][k] | s_dup[1][k] | s_dup[2][k] | s_dup[3][k];
+    const bool dup = ha_is_dup(s_dup, k);
     const bool first = valid && !dup;
     double fo = 0.0;
     long long so_ = 0;
@@ -2516,41 +2512,18 @@ __device__ __forceinline__ BookRec ha_book_pipe(const HaDev& P, const HaSearch& 
   const double own_f = bf;  // (SPEC) the thread's least, before the reductions overwrite bf / bs / bp
   const long long own_s = bs;
   // the thread's own best entry's payload, its latency behind the reductions
-  long long pay[11];
+  long long pay[NP_N + 1];
 #pragma unroll
-  for (int e = 0; e < 11; e++) pay[e] = 0;
+  for (int e = 0; e < NP_N + 1; e++) pay[e] = 0;
   if (bp >= 0) {
-    const size_t q = base + bp;
-    pay[0] = Q.oid[q];
-    pay[1] = __double_as_longlong(Q.og[q]);
-    pay[2] = Q.oix[q];
-#pragma unroll
-    for (int e = 0; e < 3; e++) pay[3 + e] = __double_as_longlong(Q.ost[q * 3 + e]);
-    pay[6] = Q.orw[q];
-#pragma unroll
-    for (int e = 0; e < 3; e++) pay[7 + e] = __double_as_longlong(Q.otuv[q * 3 + e]);
+    ha_entry_pay(Q, base + bp, pay);
   }
   const int own = bp;
-  key_min_dpp<0xB1>(bf, bs, bp);
-  key_min_dpp<0x4E>(bf, bs, bp);
-  key_min_dpp<0x141>(bf, bs, bp);
-  key_min_dpp<0x140>(bf, bs, bp);
-  {
-    double wf = __longlong_as_double(readlane_l(__double_as_longlong(bf), 0));
-    long long ws = readlane_l(bs, 0);
-    int wp_ = __builtin_amdgcn_readlane(bp, 0);
+  key_min_wave(bf, bs, bp);
+  if (lane == 0) { r_f[wave] = bf; r_s[wave] = bs; r_p[wave] = bp; }
+  if (bp >= 0 && own == bp) {
 #pragma unroll
-    for (int q = 1; q < 4; q++) {
-      const double of_ = __longlong_as_double(readlane_l(__double_as_longlong(bf), 16 * q));
-      const long long os = readlane_l(bs, 16 * q);
-      const int op = __builtin_amdgcn_readlane(bp, 16 * q);
-      if (op >= 0 && (wp_ < 0 || key_before(of_, os, wf, ws))) { wf = of_; ws = os; wp_ = op; }
-    }
-    if (lane == 0) { r_f[wave] = wf; r_s[wave] = ws; r_p[wave] = wp_; }
-    if (wp_ >= 0 && own == wp_) {
-#pragma unroll
-      for (int e = 0; e < 10; e++) r_pay[wave][e] = pay[e];
-    }
+    for (int e = 0; e < NP_N; e++) r_pay[wave][e] = pay[e];
   }
   __syncthreads();
   PSTAMP(7);
@@ -2563,77 +2536,56 @@ __device__ __forceinline__ BookRec ha_book_pipe(const HaDev& P, const HaSearch& 
     if (lane < NT / 64 && r_p[lane] >= 0) { cf = r_f[lane]; cs = r_s[lane]; cp = r_p[lane]; src = lane; }
     if (myp >= 0 && (cp < 0 || key_before(tf, nseq, cf, cs))) { cf = tf; cs = nseq; cp = myp; src = 64 + lane; }
     const int mine = cp, msrc = src;
-    key_min_dpp<0xB1>(cf, cs, cp);
-    key_min_dpp<0x4E>(cf, cs, cp);
-    key_min_dpp<0x141>(cf, cs, cp);
-    key_min_dpp<0x140>(cf, cs, cp);
-    double wf = __longlong_as_double(readlane_l(__double_as_longlong(cf), 0));
-    long long ws = readlane_l(cs, 0);
-    int wpos = __builtin_amdgcn_readlane(cp, 0);
-#pragma unroll
-    for (int q = 1; q < 4; q++) {
-      const double of_ = __longlong_as_double(readlane_l(__double_as_longlong(cf), 16 * q));
-      const long long os = readlane_l(cs, 16 * q);
-      const int op = __builtin_amdgcn_readlane(cp, 16 * q);
-      if (op >= 0 && (wpos < 0 || key_before(of_, os, wf, ws))) { wf = of_; ws = os; wpos = op; }
-    }
+    key_min_wave(cf, cs, cp);
+    const int wpos = cp;
     const bool go = !(n_open == 0 || loop >= Q.mp);
     // the winner's lane writes its payload to LDS (an old entry's from its wave record, a lane's own values)
     if (go && mine == wpos && mine >= 0) {
       if (msrc < 64) {
 #pragma unroll
-        for (int e = 0; e < 10; e++) s_win[e] = r_pay[msrc][e];
+        for (int e = 0; e < NP_N; e++) s_win[e] = r_pay[msrc][e];
       } else {
-        s_win[0] = id;
-        s_win[1] = __double_as_longlong(tg);
-        s_win[2] = nix;
-        s_win[3] = __double_as_longlong(nst0);
-        s_win[4] = __double_as_longlong(nst1);
-        s_win[5] = __double_as_longlong(nst2);
-        s_win[6] = nrw;
-        s_win[7] = __double_as_longlong(nt0);
-        s_win[8] = __double_as_longlong(nt1);
-        s_win[9] = __double_as_longlong(nt2);
+        ha_lane_pay(s_win, id, tg, nix, nst0, nst1, nst2, nrw, nt0, nt1, nt2);
       }
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the winner's LDS writes before the wave reads them
     // (SPEC) the pop is the previous runner-up: same node id, state and stored commands (the inputs of its
     // expansion and of RS_connected), so both were made speculatively
     bool hit = false;
-    if (SPEC && go && sr[10]) {
-      hit = s_win[0] == sr[0];
+    if (SPEC && go && sr[NP_N]) {
+      hit = s_win[NP_ID] == sr[NP_ID];
 #pragma unroll
-      for (int e = 3; e < 10; e++) hit = hit && s_win[e] == sr[e];
+      for (int e = NP_ST; e < NP_N; e++) hit = hit && s_win[e] == sr[e];
     }
     if (E.ngr_pub) {
       // publish the next node as tagged granules (ha_publish_node): no drain, no separate flag; the node
       // buffers too, for the next launch's RS_connected (a launch boundary orders those)
-      long long wv[10];
+      long long wv[NP_N];
 #pragma unroll
-      for (int e = 0; e < 10; e++) wv[e] = go ? s_win[e] : 0;
+      for (int e = 0; e < NP_N; e++) wv[e] = go ? s_win[e] : 0;
       ha_publish_node(Q.ngr + ((size_t)(it & (HA_NGR_SLOTS - 1)) * B + b) * HA_NGR, (unsigned)it + 1, lane, wv,
                       go ? 1u | (hit ? 2u : 0u) : 0u);
       if (go && lane < 3) {
-        Q.node[(size_t)(it & 1) * 3 * B + 3 * b + lane] = __longlong_as_double(s_win[3 + lane]);
-        Q.node_tuv[(size_t)(it & 1) * 3 * B + 3 * b + lane] = __longlong_as_double(s_win[7 + lane]);
+        Q.node[(size_t)(it & 1) * 3 * B + 3 * b + lane] = __longlong_as_double(s_win[NP_ST + lane]);
+        Q.node_tuv[(size_t)(it & 1) * 3 * B + 3 * b + lane] = __longlong_as_double(s_win[NP_TUV + lane]);
       }
-      if (go && lane == 0) Q.node_rw[(size_t)(it & 1) * B + b] = (int)s_win[6];
+      if (go && lane == 0) Q.node_rw[(size_t)(it & 1) * B + b] = (int)s_win[NP_RW];
     } else {
       if (go) {
         // publish the next node: state, stored commands, then the ready flag (the expansion blocks spin on it)
         if (lane < 3) {
-          st_ag(Q.node + (size_t)(it & 1) * 3 * B + 3 * b + lane, __longlong_as_double(s_win[3 + lane]));
-          st_ag(Q.node_tuv + (size_t)(it & 1) * 3 * B + 3 * b + lane, __longlong_as_double(s_win[7 + lane]));
+          st_ag(Q.node + (size_t)(it & 1) * 3 * B + 3 * b + lane, __longlong_as_double(s_win[NP_ST + lane]));
+          st_ag(Q.node_tuv + (size_t)(it & 1) * 3 * B + 3 * b + lane, __longlong_as_double(s_win[NP_TUV + lane]));
         }
-        if (lane == 0) st_ag(Q.node_rw + (size_t)(it & 1) * B + b, (int)s_win[6]);
+        if (lane == 0) st_ag(Q.node_rw + (size_t)(it & 1) * B + b, (int)s_win[NP_RW]);
       }
       ha_stores_done();
       if (lane == 0) st_ag(Q.nx + b, 2 * it + 2 + (go ? 1 : 0));
     }
     if (lane == 0) {
       s_go = go;
-      s_win[10] = wpos;
-      if (SPEC) s_win[11] = hit;
+      s_win[WIN_POS] = wpos;
+      if (SPEC) s_win[WIN_HIT] = hit;
     }
     PSTAMP(8);
   }
@@ -2644,7 +2596,7 @@ __device__ __forceinline__ BookRec ha_book_pipe(const HaDev& P, const HaSearch& 
     // iteration's chain.  The candidate's owner stages its payload: a lane's own entry, the thread's least from
     // the registers the pop's scan filled, its second from the open list (read before this iteration's writes)
     __syncthreads();  // the pop's position and go
-    const int wpos = (int)s_win[10];
+    const int wpos = (int)s_win[WIN_POS];
     if (s_go) {  // block-uniform
       double cf = own_f;
       long long cs = own_s;
@@ -2653,47 +2605,20 @@ __device__ __forceinline__ BookRec ha_book_pipe(const HaDev& P, const HaSearch& 
       bool cl = false;
       if (myp >= 0 && myp != wpos && (cp < 0 || key_before(tf, nseq, cf, cs))) { cf = tf; cs = nseq; cp = myp; cl = true; }
       const int cand = cp;
-      key_min_dpp<0xB1>(cf, cs, cp);
-      key_min_dpp<0x4E>(cf, cs, cp);
-      key_min_dpp<0x141>(cf, cs, cp);
-      key_min_dpp<0x140>(cf, cs, cp);
-      double wf = __longlong_as_double(readlane_l(__double_as_longlong(cf), 0));
-      long long ws = readlane_l(cs, 0);
-      int wp_ = __builtin_amdgcn_readlane(cp, 0);
-#pragma unroll
-      for (int q = 1; q < 4; q++) {
-        const double of_ = __longlong_as_double(readlane_l(__double_as_longlong(cf), 16 * q));
-        const long long os = readlane_l(cs, 16 * q);
-        const int op = __builtin_amdgcn_readlane(cp, 16 * q);
-        if (op >= 0 && (wp_ < 0 || key_before(of_, os, wf, ws))) { wf = of_; ws = os; wp_ = op; }
-      }
+      key_min_wave(cf, cs, cp);
+      const double wf = cf;
+      const long long ws = cs;
+      const int wp_ = cp;
       if (lane == 0) { u_f[wave] = wf; u_s[wave] = ws; u_p[wave] = wp_; }
       if (wp_ >= 0 && cand == wp_) {
         long long* u = u_pay[SPEC ? wave : 0];
         if (cl) {
-          u[0] = id;
-          u[1] = __double_as_longlong(tg);
-          u[2] = nix;
-          u[3] = __double_as_longlong(nst0);
-          u[4] = __double_as_longlong(nst1);
-          u[5] = __double_as_longlong(nst2);
-          u[6] = nrw;
-          u[7] = __double_as_longlong(nt0);
-          u[8] = __double_as_longlong(nt1);
-          u[9] = __double_as_longlong(nt2);
+          ha_lane_pay(u, id, tg, nix, nst0, nst1, nst2, nrw, nt0, nt1, nt2);
         } else if (cand == own) {
 #pragma unroll
-          for (int e = 0; e < 10; e++) u[e] = pay[e];
+          for (int e = 0; e < NP_N; e++) u[e] = pay[e];
         } else {
-          const size_t q = base + cand;
-          u[0] = Q.oid[q];
-          u[1] = __double_as_longlong(Q.og[q]);
-          u[2] = Q.oix[q];
-#pragma unroll
-          for (int e = 0; e < 3; e++) u[3 + e] = __double_as_longlong(Q.ost[q * 3 + e]);
-          u[6] = Q.orw[q];
-#pragma unroll
-          for (int e = 0; e < 3; e++) u[7 + e] = __double_as_longlong(Q.otuv[q * 3 + e]);
+          ha_entry_pay(Q, base + cand, u);
         }
       }
     }
@@ -2701,7 +2626,7 @@ __device__ __forceinline__ BookRec ha_book_pipe(const HaDev& P, const HaSearch& 
   }
   if (tid < 64) {
     const bool go = s_go;
-    const int wpos = (int)s_win[10];
+    const int wpos = (int)s_win[WIN_POS];
     // ---- FindNewNode's writes (as ha_book_spec)
     if (chg || app) {
       const size_t q = base + id;
@@ -2742,7 +2667,7 @@ __device__ __forceinline__ BookRec ha_book_pipe(const HaDev& P, const HaSearch& 
     // ---- popfirst!'s removal: the last entry moves into the winner's place (ha_pop)
     if (go) {
       const int last = n_open - 1;
-      const int wid = (int)s_win[0];
+      const int wid = (int)s_win[NP_ID];
       if (wpos != last) {
         // the last entry: appended (the highest appending lane), changed in place, or the old one (lane 0)
         const unsigned long long mlast = __ballot(chg && po == last);
@@ -2782,8 +2707,8 @@ __device__ __forceinline__ BookRec ha_book_pipe(const HaDev& P, const HaSearch& 
         Q.pos[base + wid] = -1;
         Q.sc_i[SI_NOPEN * B + b] = last;
         Q.sc_i[SI_CUR * B + b] = wid;
-        Q.cur_g[b] = __longlong_as_double(s_win[1]);
-        Q.cur_ix[b] = s_win[2];
+        Q.cur_g[b] = __longlong_as_double(s_win[NP_G]);
+        Q.cur_ix[b] = s_win[NP_IX];
       }
     }
   } else if (SPEC && tid < 128 && s_go) {
@@ -2793,6 +2718,8 @@ __device__ __forceinline__ BookRec ha_book_pipe(const HaDev& P, const HaSearch& 
     int cp = -1;
     if (lane < NT / 64 && u_p[lane] >= 0) { cf = u_f[lane]; cs = u_s[lane]; cp = u_p[lane]; }
     const int mine = cp;
+    // (key_min_wave written out: calling it here moved the persistent kernels' spill counts,
+    // profiles/ha_book_resources.txt)
     key_min_dpp<0xB1>(cf, cs, cp);
     key_min_dpp<0x4E>(cf, cs, cp);
     key_min_dpp<0x141>(cf, cs, cp);
@@ -2809,24 +2736,24 @@ __device__ __forceinline__ BookRec ha_book_pipe(const HaDev& P, const HaSearch& 
     }
     if (rpos >= 0 && mine == rpos) {  // the owner lane (lane = the candidate's wave)
 #pragma unroll
-      for (int e = 0; e < 10; e++) sr[e] = u_pay[SPEC ? lane : 0][e];
+      for (int e = 0; e < NP_N; e++) sr[e] = u_pay[SPEC ? lane : 0][e];
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the owner's LDS writes before the wave reads them
     const bool valid = rpos >= 0;
-    long long wv[10];
+    long long wv[NP_N];
 #pragma unroll
-    for (int e = 0; e < 10; e++) wv[e] = valid ? sr[e] : 0;
+    for (int e = 0; e < NP_N; e++) wv[e] = valid ? sr[e] : 0;
     // skip (no runner-up): the speculative blocks count the round and wait for the next one
     ha_publish_node(Q.ngr2 + ((size_t)(it & (HA_NGR_SLOTS - 1)) * B + b) * HA_NGR, (unsigned)it + 1, lane, wv,
                     valid ? 1u : 3u);
-    if (lane == 0) sr[10] = valid;
+    if (lane == 0) sr[NP_N] = valid;
   }
   __syncthreads();
   if (SPEC) {
-    if (hit_out) *hit_out = s_go ? (int)s_win[11] : 0;
+    if (hit_out) *hit_out = s_go ? (int)s_win[WIN_HIT] : 0;
     if (tid == 0 && s_go) {  // (diagnostics: MPGPU_HA_SPEC_STATS=1 prints the sums)
-      Q.nhit[b] += (int)s_win[11];
-      Q.nhit[B + b] += (int)sr[10];
+      Q.nhit[b] += (int)s_win[WIN_HIT];
+      Q.nhit[B + b] += (int)sr[NP_N];
     }
   }
   BookRec br;
@@ -2836,7 +2763,7 @@ __device__ __forceinline__ BookRec ha_book_pipe(const HaDev& P, const HaSearch& 
   br.v[RC_NNEW] = s_nnew;
   br.v[RC_NOPEN] = s_nopen;
   br.v[RC_CUR] = cur0;
-  br.v[RC_IW] = s_go ? s_win[2] : 0;
+  br.v[RC_IW] = s_go ? s_win[NP_IX] : 0;
   br.v[RC_N - 1] = 0;
 #undef PSTAMP
   return br;
@@ -3042,7 +2969,7 @@ template <int HWt, int NBGt, bool SPEC = true, bool AST = false>
 __global__ __launch_bounds__(64 * HWt) __attribute__((amdgpu_waves_per_eu(HWt == HW_TAIL ? kWpeTail : 3))) void ha_persist_kernel(
     HaDev P, HaSearch Q, IterArgs A, int B, int it0, double* rs_path2, unsigned char* rs_ok2, int* rs_len2) {
   __shared__ int sh_f;
-  __shared__ long long sh_run[12];  // (SPEC, the bookkeeping block) the last runner-up: payload + valid
+  __shared__ long long sh_run[NP_N + 2];  // (SPEC, the bookkeeping block) the last runner-up: payload, valid, one spare word
   // per scene: item 0 / 2 RS_connected of the even / odd iterations, item 1 the bookkeeping, items 3.. the groups
   const int np = P.n_prim, ng = (np + NBGt - 1) / NBGt, per = HA_PERSIST_PER(ng);
   const int slot = blockIdx.x / per, item = blockIdx.x % per;
@@ -3145,7 +3072,7 @@ __global__ __launch_bounds__(64 * HWt) __attribute__((amdgpu_waves_per_eu(HWt ==
   if ((int)threadIdx.x >= NTB) return;
   // the scene's chain: issued first where its CU is shared (other scenes' blocks, many scenes live)
   __builtin_amdgcn_s_setprio(3);
-  if (SPEC && threadIdx.x < 12) sh_run[threadIdx.x] = 0;  // no runner-up yet: iteration it0's pop is no hit
+  if (SPEC && threadIdx.x < NP_N + 2) sh_run[threadIdx.x] = 0;  // no runner-up yet: iteration it0's pop is no hit
   __syncthreads();
   int hit = 0;  // (SPEC) n_it is r_{it-1}: its records and RS_connected are the speculative ones
   for (int it = it0;; it++) {
