@@ -16,6 +16,7 @@
 //            with a log-sum-exp rescale into MPPICtrl (:186-190) and runs the
 //            final TrajectoryRollout (:192-198).  It resets the ticket.
 #include "mppi_device.hpp"
+#include "mppi_plan.hpp"
 #include "runtime.hpp"
 
 #include <hip/hip_ext.h>
@@ -31,11 +32,6 @@ namespace {
 
 constexpr int NT = 256;     // threads per block (4 waves)
 constexpr int RPB = NT / 2; // rollouts per block
-// Dynamic LDS budgets per block (160 KiB per CU on gfx950).  The plan kernel's static LDS is at most
-// 13,096 B (BT 512, LPR 2: sh_q 8 KiB, sh_e 2 KiB, the atan rows and bounds 2,704 B, the rest < 200 B), so one block
-// fits beside 146 KiB, and at most 7,976 B at BT 256, so two blocks fit beside 70 KiB each.
-constexpr size_t kMaxLds = 146 * 1024;
-constexpr size_t kCoLds = 70 * 1024;    // budget that keeps two blocks co-resident per CU
 
 __device__ __forceinline__ double block_reduce_min(double v, double* sh) {
   for (int o = 32; o >= 1; o >>= 1) v = nanmin(v, __shfl_xor(v, o));
@@ -94,9 +90,6 @@ struct PlanArgs {
   const int* live;                  // closed loop: scenes with live[s] == 0 are skipped (null: all run)
 };
 
-// The occupancy grid's LDS image (staged 16 bytes per lane) starts at the first 16-byte line of its region plus
-// the scene's offset within a line of the caller's buffer: up to 15 + 15 bytes into the region.
-constexpr int kGridPad = 32;
 typedef unsigned mp_v4u __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) mp_v4u mp_lds_v4u;
 typedef __attribute__((address_space(3))) const unsigned long long mp_lds_cu64;
@@ -950,281 +943,292 @@ static int make_dev_params(mp_ctx* ctx, const mp_mppi_params* p, int K, MppiDev*
   return MP_OK;
 }
 
-// the plan kernel instance for a block size, lanes per rollout and noise source
+// The plan kernel instances by block size (256 or 512: all that mppi_plan_shape picks), lanes per rollout, noise
+// source and lean (one rollout per lane with device noise only: mppi_plan_shape's predicate).
 using PlanFn = void (*)(MppiDev, PlanArgs);
-static PlanFn plan_kernel_for(int BT, int LPR, bool inl, bool lean = false) {
-  if (lean) {  // one rollout per lane, device noise (plan_launch's predicate)
-    if (BT == 256 && LPR == 1 && inl) return mppi_plan_kernel<256, 1, true, true>;
-    if (BT == 512 && LPR == 1 && inl) return mppi_plan_kernel<512, 1, true, true>;
-    return nullptr;
-  }
-#define MP_PLAN_CASE(bt, lpr) \
-  if (BT == bt && LPR == lpr) return inl ? mppi_plan_kernel<bt, lpr, true> : mppi_plan_kernel<bt, lpr, false>;
-  MP_PLAN_CASE(128, 1)
-  MP_PLAN_CASE(128, 2)
-  MP_PLAN_CASE(256, 1)
-  MP_PLAN_CASE(256, 2)
-  MP_PLAN_CASE(512, 1)
-  MP_PLAN_CASE(512, 2)
-#undef MP_PLAN_CASE
+struct PlanInst { int BT, LPR; bool inl, lean; PlanFn fn; };
+#define MP_PLAN_INST(bt, lpr) \
+  {bt, lpr, true, false, mppi_plan_kernel<bt, lpr, true>}, {bt, lpr, false, false, mppi_plan_kernel<bt, lpr, false>}
+static const PlanInst kPlanKernels[] = {{256, 1, true, true, mppi_plan_kernel<256, 1, true, true>},
+                                        {512, 1, true, true, mppi_plan_kernel<512, 1, true, true>},
+                                        MP_PLAN_INST(256, 1), MP_PLAN_INST(256, 2), MP_PLAN_INST(512, 1), MP_PLAN_INST(512, 2)};
+#undef MP_PLAN_INST
+static PlanFn plan_kernel_for(int BT, int LPR, bool inl, bool lean) {
+  for (const PlanInst& k : kPlanKernels)
+    if (k.BT == BT && k.LPR == LPR && k.inl == inl && k.lean == lean) return k.fn;
   return nullptr;
 }
 
-static int plan_launch(mp_ctx* ctx, const MppiDev& D, int S, const double* X0, const double* goal,
-                       const double* U_nom, const double* obstacles, const uint8_t* grid, const double* noise,
-                       double* U_out, double* traj_out, double* cost_out, int32_t* feasible_out,
-                       int32_t* rc_out, int32_t* fc_out, double* coll_traj, double* coll_ctrl,
-                       double* coll_cost, uint8_t* coll_feas, int final_stream, const int* live = nullptr) {
-  const int K = D.K, H = D.H;
-  // 8-wave blocks once the launch fills every CU with one (the dispatcher then places
-  // exactly two waves per SIMD; with 4-wave blocks, two per CU, it can stack 3 + 1 and
-  // the slowest SIMD sets the end time), else 4-wave blocks for more CUs at small S.
-  // One rollout per lane once that gives every SIMD two waves (S*K >= 2 x 256 CUs x 4 SIMDs x
-  // 64 lanes).  Measured (cfg2, K=8192, H=50): 16 scenes, LPR 1 (2 waves/SIMD, the tire chains
-  // interleaved in a lane, costs evaluated once) 0.536 ms vs LPR 2 (4 waves/SIMD) 0.703 ms;
-  // 8 scenes, LPR 1 (1 wave/SIMD) 0.384 ms vs LPR 2 (2 waves/SIMD) 0.375 ms: a lone wave
-  // cannot cover the fp64 dependency latency.
-  // With n calls in flight on n contexts (calls_in_flight), the other calls' waves fill the SIMDs too, so the
-  // rollouts of all of them count: 8 scenes, two calls alternating over two contexts, LPR 1 1.17-1.19e10
-  // rollout-steps/s against LPR 2 1.08-1.10e10; three calls 1.31e10 (r06y, bench driver arguments).
-  // (test hook) MPGPU_LPR = 1 / 2 forces the layout: the results are the same bits either way
-  // (tests/test_gpu_mppi_lane.py), only the launch shape changes
+// The pointers of a plan call in three groups: on the device for plan_launch, on the host in the entry points.
+struct PlanIn {  // scene inputs
+  const double *X0, *goal, *U_nom, *obstacles;
+  const uint8_t* grid;
+  const double* noise;
+};
+struct PlanOut {  // the plan's results
+  double *U, *traj, *cost;
+  int32_t *feasible, *rc, *fc;
+};
+struct PlanColl {  // the TrajectoryCollection outputs, each optional
+  double *traj, *ctrl, *cost;
+  uint8_t* feas;
+};
+
+// The launch shape of this call (mppi_plan.hpp).  The two test hooks are read on every call, because the tests
+// change them between calls: MPGPU_LPR = 1 / 2 forces the layout, MPGPU_PLAN_LEAN=0 the generic instance and its
+// LDS choice.  The results are the same bits either way (tests/test_gpu_mppi_lane.py, test_gpu_mppi_lean.py).
+static MppiShape plan_shape_for(const MppiDev& D, int S, const PlanIn& in, const PlanColl& coll) {
   const char* lpr_s = getenv("MPGPU_LPR");
-  const int lpr_env = lpr_s ? atoi(lpr_s) : 0;
-  const int LPR = lpr_env == 1 || lpr_env == 2 ? lpr_env : ((size_t)S * K * D.in_flight >= 131072 ? 1 : 2);
-  // Single scene (64 blocks): BT 128 (2 waves per CU on 128 CUs) 0.278 ms vs BT 256 (4 waves, one per
-  // SIMD, on 64 CUs) 0.242 ms -- a CU's four SIMDs each holding one wave beat half-filled CUs.
-  const int BT = LPR == 1 ? ((size_t)S * ((K + 511) / 512) >= 256 ? 512 : 256)
-                          : ((size_t)S * ((K + 255) / 256) >= 256 ? 512 : 256);
-  const int RPBh = BT / LPR;
-  const int nb = (K + RPBh - 1) / RPBh;
-  const int pstride = 4 + 2 * H;
-  PlanArgs A;
-  A.live = live;
-  A.X0 = X0; A.goal = goal; A.unom = U_nom; A.obs = D.n_obs > 0 ? obstacles : nullptr;
-  A.grid = D.gnx > 0 ? grid : nullptr;
-  A.inline_noise = D.noise_mode == MP_NOISE_PHILOX;
+  const char* lean_s = getenv("MPGPU_PLAN_LEAN");
+  return mppi_plan_shape({S, D.K, D.H, D.n_obs, D.gnx, D.gny, D.in_flight, D.noise_mode == MP_NOISE_PHILOX,
+                          D.ctrl_cost != 0, in.grid != nullptr, coll.traj && coll.ctrl, lpr_s ? atoi(lpr_s) : 0,
+                          !(lean_s && lean_s[0] == '0' && !lean_s[1])});
+}
+
+// Noise preparation and the workspaces of a launch: A's noise, per-rollout costs and flags, block partials,
+// tickets and the control lists' HBM home.
+static int plan_buffers(mp_ctx* ctx, const MppiDev& D, int S, const MppiShape& P, const PlanIn& in,
+                        const PlanColl& coll, PlanArgs& A) {
+  const int K = D.K, H = D.H;
   A.noise = nullptr;
   if (!A.inline_noise) {  // caller's z (parity mode): transposed h-major by noise_prep_kernel
     double* zh = (double*)mp_ws(ctx, WS_NOISE, sizeof(double) * (size_t)S * K * H * 2);
     if (!zh) return MP_ERR_NOMEM;
     const long long n = (long long)S * K * H;
-    hipLaunchKernelGGL(noise_prep_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, D, S, noise,
+    hipLaunchKernelGGL(noise_prep_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, D, S, in.noise,
                        zh);
     MP_HIP(ctx, hipGetLastError());
     A.noise = zh;
   }
-  A.cost_all = coll_cost ? coll_cost : (double*)mp_ws(ctx, WS_MPPI_COST, sizeof(double) * (size_t)S * K);
-  A.feas_all = coll_feas ? coll_feas : (unsigned char*)mp_ws(ctx, WS_MPPI_FEAS, (size_t)S * K);
-  A.part = (double*)mp_ws(ctx, WS_MPPI_PART, sizeof(double) * (size_t)S * nb * pstride);
+  A.cost_all = coll.cost ? coll.cost : (double*)mp_ws(ctx, WS_MPPI_COST, sizeof(double) * (size_t)S * K);
+  A.feas_all = coll.feas ? coll.feas : (unsigned char*)mp_ws(ctx, WS_MPPI_FEAS, (size_t)S * K);
+  A.part = (double*)mp_ws(ctx, WS_MPPI_PART, sizeof(double) * (size_t)S * P.nb * P.pstride);
   if (!A.cost_all || !A.feas_all || !A.part) return MP_ERR_NOMEM;
-  A.coll_traj = coll_traj;
   int st = mp_ticket_reserve(ctx, S);
   if (st) return st;
   A.tickets = ctx->tickets;
   A.flags = ctx->flags;
-  A.U_out = U_out; A.traj_out = traj_out; A.cost_out = cost_out; A.feas_out = feasible_out;
-  A.rc_out = rc_out; A.fc_out = fc_out;
-  A.nb = nb;
-  A.pstride = pstride;
-  // dynamic LDS: [phase-2: 2H + nb] [unom: 2H] [obs: 3 n_obs] [grid bytes] [control lists | staged partials]
-  int off = 2 * H + nb;
-  A.lds_unom = off;
-  off += 2 * H;
-  A.lds_cq = off;
-  off += 2 * H;
-  A.lds_obs = off;
-  off += 3 * D.n_obs;
-  const size_t gbytes = (size_t)D.gnx * D.gny;
-  A.lds_grid = -1;
-  if (D.gnx > 0 && (size_t)off * 8 + gbytes + kGridPad <= 48 * 1024) {
-    A.lds_grid = off;
-    off += (int)((gbytes + kGridPad + 7) / 8);
-  }
-  // Control lists / staged partials in LDS only while two blocks still fit per CU
-  // (multi-scene launches need every block co-resident); otherwise the HBM path.
-  const int ctrl_words = RPBh * (2 * H + 1), part_words = nb * pstride;
-  A.lds_ctrl = A.lds_part = -1;
-  const bool many = (size_t)S * nb > 256;  // more blocks than CUs: keep two per CU resident
-  const size_t budget = many ? kCoLds : kMaxLds;
-  // The lean instance (mppi_plan_kernel<.., LEAN>) for the common collecting call: one rollout per lane,
-  // device noise, no circle obstacles, the grid in LDS, the control cost on, both collection outputs, and
-  // K < 2^27 (32-bit lane offsets of 16 K bytes).  Such a call keeps no control lists in LDS: they go to
-  // coll_ctrl anyway, and the block partial sums them from there over the same rollouts in the same order
-  // (the LDS path only adds the inactive lanes' 0.0 * u).
-  // (test hook) MPGPU_PLAN_LEAN=0 forces the generic instance and its LDS choice, read per call as MPGPU_LPR is.
-  const char* lean_s = getenv("MPGPU_PLAN_LEAN");
-  const bool lean = !(lean_s && lean_s[0] == '0' && !lean_s[1]) && LPR == 1 && (BT == 256 || BT == 512) && A.inline_noise &&
-                    D.n_obs == 0 && A.grid && A.lds_grid >= 0 && D.ctrl_cost && coll_traj && coll_ctrl &&
-                    K < (1 << 27);
-  if (lean) {
-    if ((size_t)(off + part_words) * 8 <= budget) {
-      A.lds_part = off;
-      off += part_words;
-    }
-  } else if ((size_t)(off + (ctrl_words > part_words ? ctrl_words : part_words)) * 8 <= budget) {
-    A.lds_ctrl = A.lds_part = off;
-    off += ctrl_words > part_words ? ctrl_words : part_words;
-  } else if ((size_t)(off + part_words) * 8 <= budget) {
-    A.lds_part = off;
-    off += part_words;
-  }
   // control lists in HBM: the TrajectoryCollection output, or the fallback when LDS is too small
-  A.ctrl_all = coll_ctrl;
-  if (A.lds_ctrl < 0 && !A.ctrl_all) {
+  A.ctrl_all = coll.ctrl;
+  if (P.lds_ctrl < 0 && !A.ctrl_all) {
     A.ctrl_all = (double*)mp_ws(ctx, WS_IO14, sizeof(double) * (size_t)S * K * 2 * H);
     if (!A.ctrl_all) return MP_ERR_NOMEM;
   }
-  const size_t shmem = sizeof(double) * (size_t)off;
-  MP_CHECK(ctx, shmem <= kMaxLds, "K/H/obstacles too large for one scene (dynamic LDS %zu B)", shmem);
-  if (!ctx->mppi_lds_attr) {
-    MP_HIP(ctx, hipSetDevice(ctx->device));  // the attribute applies to the current device
-    for (int bt : {128, 256, 512})
-      for (int lpr : {1, 2})
-        for (bool inl : {false, true})
-          MP_HIP(ctx, hipFuncSetAttribute((const void*)plan_kernel_for(bt, lpr, inl),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds));
-    for (int bt : {256, 512})
-      MP_HIP(ctx, hipFuncSetAttribute((const void*)plan_kernel_for(bt, 1, true, true),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds));
-    ctx->mppi_lds_attr = true;
+  return MP_OK;
+}
+
+// Once per context: every plan kernel instance may use kMaxLds of dynamic LDS.
+static int plan_kernel_attrs(mp_ctx* ctx) {
+  if (ctx->mppi_lds_attr) return MP_OK;
+  MP_HIP(ctx, hipSetDevice(ctx->device));  // the attribute applies to the current device
+  for (const PlanInst& k : kPlanKernels)
+    MP_HIP(ctx, hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds));
+  ctx->mppi_lds_attr = true;
+  return MP_OK;
+}
+
+// Deferred final rollout: the snapshot ring slot of this call (*par), free once the final rollout of the call
+// MP_FIN_RING back (same slot) is done.
+static int fin_slot_acquire(mp_ctx* ctx, const MppiDev& D, int S, PlanArgs& A, int* par) {
+  int st = mp_side_init(ctx);
+  if (st) return st;
+  *par = ctx->fin_par;
+  ctx->fin_par = (*par + 1) % MP_FIN_RING;
+  const FinRec R(D.H, D.n_obs, D.gnx * D.gny);
+  A.fin_stride = R.stride;
+  // every slot of the ring sized at once: a slot first used by a later call would allocate (hipMalloc, which
+  // can wait for the device) in the middle of a run of calls -- with calls alternating over two contexts, the
+  // bench's first timed calls did
+  for (int q = 0; q < MP_FIN_RING; q++)
+    if (!mp_ws(ctx, WS_FIN0 + q, sizeof(double) * (size_t)S * R.stride)) return MP_ERR_NOMEM;
+  A.fin = (double*)mp_ws(ctx, WS_FIN0 + *par, sizeof(double) * (size_t)S * R.stride);
+  // The host (not the context stream) waits for the final rollout MP_FIN_RING calls back to
+  // have read this slot (long done): a cross-stream wait packet would stall the context
+  // stream between kernels, and a wait on the previous call's final rollout (which runs
+  // beside the next plan kernel) would hold the host back until the GPU idles.
+  MP_HIP(ctx, hipEventSynchronize(ctx->ev_fin[*par]));
+  return MP_OK;
+}
+
+// The plan launch.  Timing events ride on the dispatch packet (hipExtLaunchKernel), and the stop event
+// (*plan_done, null without kernel timing) doubles as the side stream's plan-done dependency: no marker packets
+// between consecutive plans.
+static int plan_enqueue(mp_ctx* ctx, const MppiDev& D, int S, const MppiShape& P, const PlanArgs& A,
+                        hipEvent_t* plan_done) {
+  hipEvent_t t_start;
+  mp_time_pair(ctx, &t_start, plan_done);
+  void* args[] = {(void*)&D, (void*)&A};
+  MP_HIP(ctx, hipExtLaunchKernel((const void*)plan_kernel_for(P.BT, P.LPR, A.inline_noise != 0, P.lean), dim3(S * P.nb),
+                                 dim3(P.BT), args, sizeof(double) * P.lds_words, ctx->stream, t_start, *plan_done, 0));
+  MP_HIP(ctx, hipGetLastError());
+  return MP_OK;
+}
+
+// The final rollout of ring slot `par` on the side stream, after the plan kernel (plan_done, or an event recorded
+// here when the launch carried none).
+static int final_rollout_enqueue(mp_ctx* ctx, const MppiDev& D, int S, const PlanArgs& A, int par,
+                                 hipEvent_t plan_done, const PlanOut& out) {
+  const FinRec R(D.H, D.n_obs, D.gnx * D.gny);
+  const int grid_lds = (size_t)R.stride * 8 <= 64 * 1024;
+  const size_t fsh = sizeof(double) * (size_t)(grid_lds ? R.stride : R.grid);
+  MP_CHECK(ctx, fsh <= kMaxLds, "final rollout snapshot too large for LDS (%zu B)", fsh);
+  if (!ctx->fin_lds_attr) {
+    MP_HIP(ctx, hipSetDevice(ctx->device));
+    MP_HIP(ctx, hipFuncSetAttribute((const void*)final_rollout_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)kMaxLds));
+    ctx->fin_lds_attr = true;
   }
-  // deferred final rollout: snapshot ring slot of this call, free once the final rollout of
-  // the call MP_FIN_RING back (same slot) is done
+  if (!plan_done) {
+    plan_done = ctx->ev_plan[par];
+    MP_HIP(ctx, hipEventRecord(plan_done, ctx->stream));
+  }
+  MP_HIP(ctx, hipStreamWaitEvent(ctx->side, plan_done, 0));
+  hipLaunchKernelGGL(final_rollout_kernel, dim3(S), dim3(64), fsh, ctx->side, D, A.fin, A.fin_stride, grid_lds,
+                     out.traj, out.cost, out.feasible, ctx->flags);
+  MP_HIP(ctx, hipGetLastError());
+  MP_HIP(ctx, hipEventRecord(ctx->ev_fin[par], ctx->side));
+  return MP_OK;
+}
+
+// (diagnostic) MPGPU_STAMPS: 32 clock words per block, written by MP_STAMP and reported per call on stderr in
+// the form tools/stamps.py reads
+static bool stamps_on() {
+  static const bool on = getenv("MPGPU_STAMPS") != nullptr;
+  return on;
+}
+
+static int stamps_begin(mp_ctx* ctx, int nblk, PlanArgs& A) {
+  const size_t bytes = sizeof(unsigned long long) * 32 * nblk;
+  A.stamps = (unsigned long long*)mp_ws(ctx, WS_HA2, bytes);
+  if (!A.stamps) return MP_ERR_NOMEM;
+  MP_HIP(ctx, hipMemsetAsync(A.stamps, 0, bytes, ctx->stream));
+  return MP_OK;
+}
+
+static void stamps_percentiles(const char* what, std::vector<double>& v) {
+  std::sort(v.begin(), v.end());
+  const size_t n = v.size();
+  fprintf(stderr, " | %s p0/50/90/100 %.1f %.1f %.1f %.1f", what, v[0], v[n / 2], v[n * 9 / 10], v[n - 1]);
+}
+
+static int stamps_report(mp_ctx* ctx, const unsigned long long* stamps, int nblk) {
+  std::vector<unsigned long long> h((size_t)32 * nblk);
+  MP_HIP(ctx, hipMemcpyAsync(h.data(), stamps, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+  MP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  unsigned long long t0 = ~0ull, end = 0;
+  double d01 = 0, d12 = 0, d23 = 0;
+  int last = -1;
+  for (int b = 0; b < nblk; b++) {
+    const unsigned long long* q = &h[32 * b];
+    t0 = q[0] < t0 ? q[0] : t0;
+    d01 += (q[1] - q[0]) / 100.0; d12 += (q[2] - q[1]) / 100.0; d23 += (q[3] - q[2]) / 100.0;
+    if (q[5]) last = b;
+    end = q[5] > end ? q[5] : end;
+    end = q[3] > end ? q[3] : end;
+  }
+  auto us = [&](unsigned long long t) { return (t - t0) / 100.0; };
+  fprintf(stderr, "[stamps us] blocks=%d mean rollout %.2f partial %.2f ticket %.2f", nblk, d01 / nblk, d12 / nblk,
+          d23 / nblk);
+  // spread: block start times and phase-1 end times; per-wave ends and SIMD placement; per-XCC wave-end mean /
+  // max and block count
+  std::vector<double> st, en, we;
+  int hist[9] = {0};  // max waves on one SIMD within a block
+  double sum[16] = {0}, mx[16] = {0};
+  int cnt[16] = {0}, nbk[16] = {0};
+  for (int b = 0; b < nblk; b++) {
+    const unsigned long long* q = &h[32 * b];
+    st.push_back(us(q[0]));
+    en.push_back(us(q[1]));
+    const int x = (int)(q[30] & 15);
+    nbk[x]++;
+    int on_simd[4] = {0, 0, 0, 0}, most = 0;
+    for (int w = 0; w < 8; w++) {
+      if (!q[8 + w]) continue;
+      const double v = us(q[8 + w]);
+      we.push_back(v);
+      most = std::max(most, ++on_simd[(q[20 + w] >> 4) & 3]);
+      sum[x] += v; cnt[x]++; mx[x] = std::max(mx[x], v);
+    }
+    hist[most]++;
+  }
+  stamps_percentiles("start", st);
+  stamps_percentiles("p1-end", en);
+  stamps_percentiles("wave-end", we);
+  fprintf(stderr, " | blocks by max waves/SIMD 1:%d 2:%d 3:%d 4:%d", hist[1], hist[2], hist[3], hist[4]);
+  fprintf(stderr, " | xcc(blocks mean/max):");
+  for (int x = 0; x < 16; x++)
+    if (cnt[x]) fprintf(stderr, " %d(%d %.1f/%.1f)", x, nbk[x], sum[x] / cnt[x], mx[x]);
+  if (last >= 0) {
+    const unsigned long long* q = &h[32 * last];
+    fprintf(stderr, " | last block: start+%.2f combine %.2f final-rollout %.2f | total %.2f", us(q[0]),
+            (q[4] - q[3]) / 100.0, (q[5] - q[4]) / 100.0, us(end));
+  }
+  fprintf(stderr, "\n");
+  return MP_OK;
+}
+
+// One MPPIPlan launch for S scenes on the context stream (device pointers), and with final_stream the deferred
+// final rollout on the side stream.
+static int plan_launch(mp_ctx* ctx, const MppiDev& D, int S, const PlanIn& in, const PlanOut& out,
+                       const PlanColl& coll, int final_stream, const int* live = nullptr) {
+  const MppiShape P = plan_shape_for(D, S, in, coll);
+  const size_t shmem = sizeof(double) * P.lds_words;
+  MP_CHECK(ctx, shmem <= kMaxLds, "K/H/obstacles too large for one scene (dynamic LDS %zu B)", shmem);
+  PlanArgs A;
+  A.live = live;
+  A.X0 = in.X0; A.goal = in.goal; A.unom = in.U_nom; A.obs = D.n_obs > 0 ? in.obstacles : nullptr;
+  A.grid = D.gnx > 0 ? in.grid : nullptr;
+  A.inline_noise = D.noise_mode == MP_NOISE_PHILOX;
+  A.coll_traj = coll.traj;
+  A.U_out = out.U; A.traj_out = out.traj; A.cost_out = out.cost; A.feas_out = out.feasible;
+  A.rc_out = out.rc; A.fc_out = out.fc;
+  A.nb = P.nb;
+  A.pstride = P.pstride;
+  A.lds_unom = P.lds_unom; A.lds_cq = P.lds_cq; A.lds_obs = P.lds_obs; A.lds_grid = P.lds_grid;
+  A.lds_ctrl = P.lds_ctrl; A.lds_part = P.lds_part;
+  int st = plan_buffers(ctx, D, S, P, in, coll, A);
+  if (st || (st = plan_kernel_attrs(ctx))) return st;
   A.fin = nullptr;
   A.fin_stride = 0;
   int par = 0;
-  if (final_stream) {
-    int st2 = mp_side_init(ctx);
-    if (st2) return st2;
-    par = ctx->fin_par;
-    ctx->fin_par = (par + 1) % MP_FIN_RING;
-    const FinRec R(H, D.n_obs, D.gnx * D.gny);
-    A.fin_stride = R.stride;
-    // every slot of the ring sized at once: a slot first used by a later call would allocate (hipMalloc, which
-    // can wait for the device) in the middle of a run of calls -- with calls alternating over two contexts, the
-    // bench's first timed calls did
-    for (int q = 0; q < MP_FIN_RING; q++)
-      if (!mp_ws(ctx, WS_FIN0 + q, sizeof(double) * (size_t)S * R.stride)) return MP_ERR_NOMEM;
-    A.fin = (double*)mp_ws(ctx, WS_FIN0 + par, sizeof(double) * (size_t)S * R.stride);
-    // The host (not the context stream) waits for the final rollout MP_FIN_RING calls back to
-    // have read this slot (long done): a cross-stream wait packet would stall the context
-    // stream between kernels, and a wait on the previous call's final rollout (which runs
-    // beside the next plan kernel) would hold the host back until the GPU idles.
-    MP_HIP(ctx, hipEventSynchronize(ctx->ev_fin[par]));
-  }
+  if (final_stream && (st = fin_slot_acquire(ctx, D, S, A, &par))) return st;
   A.stamps = nullptr;
-  static const bool stamps_on = getenv("MPGPU_STAMPS") != nullptr;
-  if (stamps_on) {
-    A.stamps = (unsigned long long*)mp_ws(ctx, WS_HA2, sizeof(unsigned long long) * 32 * S * nb);
-    MP_HIP(ctx, hipMemsetAsync(A.stamps, 0, sizeof(unsigned long long) * 32 * S * nb, ctx->stream));
-  }
-  // timing events ride on the dispatch packet (hipExtLaunchKernel), and the stop event doubles
-  // as the side stream's plan-done dependency: no marker packets between consecutive plans
-  hipEvent_t t_start, t_stop;
-  mp_time_pair(ctx, &t_start, &t_stop);
-  const dim3 grd(S * nb);
-  {
-    MppiDev Dl = D;
-    void* args[] = {(void*)&Dl, (void*)&A};
-    MP_HIP(ctx, hipExtLaunchKernel((const void*)plan_kernel_for(BT, LPR, A.inline_noise != 0, lean), grd, dim3(BT), args,
-                                   shmem, ctx->stream, t_start, t_stop, 0));
-  }
-  MP_HIP(ctx, hipGetLastError());
-  if (final_stream) {
-    const FinRec R(H, D.n_obs, D.gnx * D.gny);
-    const int grid_lds = (size_t)R.stride * 8 <= 64 * 1024;
-    const size_t fsh = sizeof(double) * (size_t)(grid_lds ? R.stride : R.grid);
-    MP_CHECK(ctx, fsh <= kMaxLds, "final rollout snapshot too large for LDS (%zu B)", fsh);
-    if (!ctx->fin_lds_attr) {
-      MP_HIP(ctx, hipSetDevice(ctx->device));
-      MP_HIP(ctx, hipFuncSetAttribute((const void*)final_rollout_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)kMaxLds));
-      ctx->fin_lds_attr = true;
-    }
-    hipEvent_t plan_done = t_stop;
-    if (!plan_done) {
-      plan_done = ctx->ev_plan[par];
-      MP_HIP(ctx, hipEventRecord(plan_done, ctx->stream));
-    }
-    MP_HIP(ctx, hipStreamWaitEvent(ctx->side, plan_done, 0));
-    hipLaunchKernelGGL(final_rollout_kernel, dim3(S), dim3(64), fsh, ctx->side, D, A.fin, A.fin_stride, grid_lds,
-                       traj_out, cost_out, feasible_out, ctx->flags);
-    MP_HIP(ctx, hipGetLastError());
-    MP_HIP(ctx, hipEventRecord(ctx->ev_fin[par], ctx->side));
-  }
-  if (stamps_on) {
-    std::vector<unsigned long long> h(32 * S * nb);
-    MP_HIP(ctx, hipMemcpyAsync(h.data(), A.stamps, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-    MP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    unsigned long long t0 = ~0ull, end = 0;
-    double d01 = 0, d12 = 0, d23 = 0;
-    int last = -1;
-    for (int b = 0; b < S * nb; b++) {
-      const unsigned long long* q = &h[32 * b];
-      t0 = q[0] < t0 ? q[0] : t0;
-      d01 += (q[1] - q[0]) / 100.0; d12 += (q[2] - q[1]) / 100.0; d23 += (q[3] - q[2]) / 100.0;
-      if (q[5]) last = b;
-      end = q[5] > end ? q[5] : end;
-      end = q[3] > end ? q[3] : end;
-    }
-    fprintf(stderr, "[stamps us] blocks=%d mean rollout %.2f partial %.2f ticket %.2f", S * nb, d01 / (S * nb),
-            d12 / (S * nb), d23 / (S * nb));
-    {  // spread: block start times and phase-1 end times (percentiles)
-      std::vector<double> st, en;
-      for (int b = 0; b < S * nb; b++) {
-        st.push_back((h[32 * b] - t0) / 100.0);
-        en.push_back((h[32 * b + 1] - t0) / 100.0);
-      }
-      std::sort(st.begin(), st.end());
-      std::sort(en.begin(), en.end());
-      const int n = S * nb;
-      fprintf(stderr, " | start p0/50/90/100 %.1f %.1f %.1f %.1f | p1-end p0/50/90/100 %.1f %.1f %.1f %.1f", st[0],
-              st[n / 2], st[n * 9 / 10], st[n - 1], en[0], en[n / 2], en[n * 9 / 10], en[n - 1]);
-      // per-wave ends and SIMD placement
-      std::vector<double> we;
-      int hist[9] = {0};  // max waves on one SIMD within a block
-      for (int b = 0; b < n; b++) {
-        int cnt[4] = {0, 0, 0, 0}, mx = 0;
-        for (int w = 0; w < 8; w++) {
-          const unsigned long long tw = h[32 * b + 8 + w];
-          if (!tw) continue;
-          we.push_back((tw - t0) / 100.0);
-          const int simd = (int)((h[32 * b + 20 + w] >> 4) & 3);
-          mx = std::max(mx, ++cnt[simd]);
-        }
-        hist[mx]++;
-      }
-      std::sort(we.begin(), we.end());
-      const int m = (int)we.size();
-      fprintf(stderr, " | wave-end p0/50/90/100 %.1f %.1f %.1f %.1f | blocks by max waves/SIMD 1:%d 2:%d 3:%d 4:%d",
-              we[0], we[m / 2], we[m * 9 / 10], we[m - 1], hist[1], hist[2], hist[3], hist[4]);
-    }
-    {  // per-XCC wave-end mean / max and block count
-      double sum[16] = {0}, mx[16] = {0};
-      int cnt[16] = {0}, nbk[16] = {0};
-      for (int b = 0; b < S * nb; b++) {
-        const int x = (int)(h[32 * b + 30] & 15);
-        nbk[x]++;
-        for (int w = 0; w < 8; w++) {
-          const unsigned long long tw = h[32 * b + 8 + w];
-          if (!tw) continue;
-          const double v = (tw - t0) / 100.0;
-          sum[x] += v; cnt[x]++; mx[x] = std::max(mx[x], v);
-        }
-      }
-      fprintf(stderr, " | xcc(blocks mean/max):");
-      for (int x = 0; x < 16; x++)
-        if (cnt[x]) fprintf(stderr, " %d(%d %.1f/%.1f)", x, nbk[x], sum[x] / cnt[x], mx[x]);
-    }
-    if (last >= 0) {
-      const unsigned long long* q = &h[32 * last];
-      fprintf(stderr, " | last block: start+%.2f combine %.2f final-rollout %.2f | total %.2f", (q[0] - t0) / 100.0,
-              (q[4] - q[3]) / 100.0, (q[5] - q[4]) / 100.0, (end - t0) / 100.0);
-    }
-    fprintf(stderr, "\n");
-  }
+  if (stamps_on() && (st = stamps_begin(ctx, S * P.nb, A))) return st;
+  hipEvent_t plan_done;
+  if ((st = plan_enqueue(ctx, D, S, P, A, &plan_done))) return st;
+  if (final_stream && (st = final_rollout_enqueue(ctx, D, S, A, par, plan_done, out))) return st;
+  return stamps_on() ? stamps_report(ctx, A.stamps, S * P.nb) : MP_OK;
+}
+
+// The argument checks the plan entry points share, in the order each of them makes them.  `outputs`: every
+// required output pointer of the call is present.
+static int check_plan_inputs(mp_ctx* ctx, const mp_mppi_params* p, const PlanIn& in, bool outputs) {
+  MP_CHECK(ctx, in.X0 && in.goal && in.U_nom && outputs, "required pointer is NULL");
+  MP_CHECK(ctx, p->noise_mode != MP_NOISE_EXTERNAL || in.noise, "noise is NULL in MP_NOISE_EXTERNAL mode");
+  MP_CHECK(ctx, p->n_obs == 0 || in.obstacles, "obstacles NULL with n_obs > 0");
+  MP_CHECK(ctx, p->grid_nx == 0 || in.grid, "grid NULL with grid_nx > 0");
   return MP_OK;
+}
+static int check_plan_call(mp_ctx* ctx, const mp_mppi_params* p, int S, const PlanIn& in, const PlanOut& out) {
+  MP_CHECK(ctx, S >= 1, "S (%d) must be >= 1", S);
+  int st = check_plan_inputs(ctx, p, in, out.U && out.traj && out.cost && out.feasible && out.rc && out.fc);
+  if (st) return st;
+  MP_CHECK(ctx, p->final_stream == 0 || p->final_stream == 1, "final_stream (%d) must be 0 or 1", p->final_stream);
+  return MP_OK;
+}
+
+// The six scene inputs of n scenes to WS_IO0..5: `host` points at the first of them, noise_n doubles of noise.
+// An input the parameters do not use (no circles, no grid, device noise) uploads nothing and stays null.
+static PlanIn upload_scene_inputs(mp_ctx* ctx, const mp_mppi_params* p, size_t n, const PlanIn& host, size_t noise_n,
+                                  int* st) {
+  PlanIn d;
+  d.X0 = mp_upload(ctx, WS_IO0, host.X0, 7 * n, st);
+  d.goal = mp_upload(ctx, WS_IO1, host.goal, 2 * n, st);
+  d.U_nom = mp_upload(ctx, WS_IO2, host.U_nom, 2 * (size_t)p->H * n, st);
+  d.obstacles = mp_upload(ctx, WS_IO3, p->n_obs ? host.obstacles : nullptr, 3 * (size_t)p->n_obs * n, st);
+  d.grid = mp_upload(ctx, WS_IO4, p->grid_nx ? host.grid : nullptr, (size_t)p->grid_nx * p->grid_ny * n, st);
+  d.noise = mp_upload(ctx, WS_IO5, p->noise_mode == MP_NOISE_EXTERNAL ? host.noise : nullptr, noise_n, st);
+  return d;
 }
 
 }  // namespace
@@ -1240,16 +1244,10 @@ int mp_mppi_plan_dev(mp_ctx* ctx, const mp_mppi_params* p, int32_t S, const doub
   MppiDev D;
   int st = make_dev_params(ctx, p, p ? p->K : 0, &D);
   if (st) return st;
-  MP_CHECK(ctx, S >= 1, "S (%d) must be >= 1", S);
-  MP_CHECK(ctx, X0 && goal && U_nom && U_out && traj_out && cost_out && feasible_out && rollout_count_out &&
-               feasible_count_out, "required pointer is NULL");
-  MP_CHECK(ctx, p->noise_mode != MP_NOISE_EXTERNAL || noise, "noise is NULL in MP_NOISE_EXTERNAL mode");
-  MP_CHECK(ctx, p->n_obs == 0 || obstacles, "obstacles NULL with n_obs > 0");
-  MP_CHECK(ctx, p->grid_nx == 0 || grid, "grid NULL with grid_nx > 0");
-  MP_CHECK(ctx, p->final_stream == 0 || p->final_stream == 1, "final_stream (%d) must be 0 or 1", p->final_stream);
-  return plan_launch(ctx, D, S, X0, goal, U_nom, obstacles, grid, noise, U_out, traj_out, cost_out, feasible_out,
-                     rollout_count_out, feasible_count_out, coll_traj, coll_ctrl, coll_cost, coll_feas,
-                     p->final_stream);
+  const PlanIn in = {X0, goal, U_nom, obstacles, grid, noise};
+  const PlanOut out = {U_out, traj_out, cost_out, feasible_out, rollout_count_out, feasible_count_out};
+  if ((st = check_plan_call(ctx, p, S, in, out))) return st;
+  return plan_launch(ctx, D, S, in, out, {coll_traj, coll_ctrl, coll_cost, coll_feas}, p->final_stream);
 }
 
 int mp_mppi_plan(mp_ctx* ctx, const mp_mppi_params* p, int32_t S, const double* X0, const double* goal,
@@ -1261,49 +1259,41 @@ int mp_mppi_plan(mp_ctx* ctx, const mp_mppi_params* p, int32_t S, const double* 
   MppiDev D;
   int st = make_dev_params(ctx, p, p ? p->K : 0, &D);
   if (st) return st;
-  MP_CHECK(ctx, S >= 1, "S (%d) must be >= 1", S);
-  MP_CHECK(ctx, X0 && goal && U_nom && U_out && traj_out && cost_out && feasible_out && rollout_count_out &&
-               feasible_count_out, "required pointer is NULL");
-  MP_CHECK(ctx, p->noise_mode != MP_NOISE_EXTERNAL || noise, "noise is NULL in MP_NOISE_EXTERNAL mode");
-  MP_CHECK(ctx, p->n_obs == 0 || obstacles, "obstacles NULL with n_obs > 0");
-  MP_CHECK(ctx, p->grid_nx == 0 || grid, "grid NULL with grid_nx > 0");
+  const PlanIn in = {X0, goal, U_nom, obstacles, grid, noise};
+  if ((st = check_plan_call(ctx, p, S, in, {U_out, traj_out, cost_out, feasible_out, rollout_count_out,
+                                            feasible_count_out})))
+    return st;
   MP_HIP(ctx, hipSetDevice(ctx->device));
   const size_t K = p->K, H = p->H;
   st = MP_OK;
-  const double* dX0 = mp_upload(ctx, WS_IO0, X0, 7 * (size_t)S, &st);
-  const double* dgoal = mp_upload(ctx, WS_IO1, goal, 2 * (size_t)S, &st);
-  const double* dun = mp_upload(ctx, WS_IO2, U_nom, 2 * H * S, &st);
-  const double* dobs = mp_upload(ctx, WS_IO3, p->n_obs ? obstacles : nullptr, 3 * (size_t)p->n_obs * S, &st);
-  const uint8_t* dgrid = mp_upload(ctx, WS_IO4, p->grid_nx ? grid : nullptr, (size_t)p->grid_nx * p->grid_ny * S, &st);
-  const double* dnoise = mp_upload(ctx, WS_IO5, p->noise_mode == MP_NOISE_EXTERNAL ? noise : nullptr, K * H * 2 * S, &st);
-  double* dU = mp_alloc_out(ctx, WS_IO6, U_out, 2 * H * S, &st);
-  double* dtraj = mp_alloc_out(ctx, WS_IO7, traj_out, (H + 1) * 7 * S, &st);
-  double* dcost = mp_alloc_out(ctx, WS_IO8, cost_out, (size_t)S, &st);
-  int32_t* dfe = mp_alloc_out(ctx, WS_IO9, feasible_out, (size_t)S, &st);
-  int32_t* drc = mp_alloc_out(ctx, WS_IO10, rollout_count_out, (size_t)S, &st);
-  int32_t* dfc = mp_alloc_out(ctx, WS_IO11, feasible_count_out, (size_t)S, &st);
-  double* dct = mp_alloc_out(ctx, WS_IO12, coll_traj, K * (H + 1) * 7 * S, &st);
-  double* dcc = mp_alloc_out(ctx, WS_IO13, coll_ctrl, K * H * 2 * S, &st);
-  double* dco = mp_alloc_out(ctx, WS_IO15, coll_cost, K * S, &st);
-  uint8_t* dcf = mp_alloc_out(ctx, WS_IO16, coll_feas, K * S, &st);
+  const PlanIn din = upload_scene_inputs(ctx, p, (size_t)S, in, K * H * 2 * S, &st);
+  PlanOut d;
+  d.U = mp_alloc_out(ctx, WS_IO6, U_out, 2 * H * S, &st);
+  d.traj = mp_alloc_out(ctx, WS_IO7, traj_out, (H + 1) * 7 * S, &st);
+  d.cost = mp_alloc_out(ctx, WS_IO8, cost_out, (size_t)S, &st);
+  d.feasible = mp_alloc_out(ctx, WS_IO9, feasible_out, (size_t)S, &st);
+  d.rc = mp_alloc_out(ctx, WS_IO10, rollout_count_out, (size_t)S, &st);
+  d.fc = mp_alloc_out(ctx, WS_IO11, feasible_count_out, (size_t)S, &st);
+  PlanColl c;
+  c.traj = mp_alloc_out(ctx, WS_IO12, coll_traj, K * (H + 1) * 7 * S, &st);
+  c.ctrl = mp_alloc_out(ctx, WS_IO13, coll_ctrl, K * H * 2 * S, &st);
+  c.cost = mp_alloc_out(ctx, WS_IO15, coll_cost, K * S, &st);
+  c.feas = mp_alloc_out(ctx, WS_IO16, coll_feas, K * S, &st);
   if (st) return st;
   MP_HIP(ctx, hipMemsetAsync(ctx->flags, 0, sizeof(int), ctx->stream));
-  MP_CHECK(ctx, p->final_stream == 0 || p->final_stream == 1, "final_stream (%d) must be 0 or 1", p->final_stream);
-  st = plan_launch(ctx, D, S, dX0, dgoal, dun, dobs, dgrid, dnoise, dU, dtraj, dcost, dfe, drc, dfc, dct, dcc,
-                   dco, dcf, p->final_stream);
-  if (st) return st;
+  if ((st = plan_launch(ctx, D, S, din, d, c, p->final_stream))) return st;
   if (p->final_stream && (st = mp_ctx_join(ctx))) return st;  // downloads below follow the side stream
   int flag = 0;
-  if ((st = mp_download(ctx, U_out, dU, 2 * H * S))) return st;
-  if ((st = mp_download(ctx, traj_out, dtraj, (H + 1) * 7 * S))) return st;
-  if ((st = mp_download(ctx, cost_out, dcost, (size_t)S))) return st;
-  if ((st = mp_download(ctx, feasible_out, dfe, (size_t)S))) return st;
-  if ((st = mp_download(ctx, rollout_count_out, drc, (size_t)S))) return st;
-  if ((st = mp_download(ctx, feasible_count_out, dfc, (size_t)S))) return st;
-  if ((st = mp_download(ctx, coll_traj, dct, K * (H + 1) * 7 * S))) return st;
-  if ((st = mp_download(ctx, coll_ctrl, dcc, K * H * 2 * S))) return st;
-  if ((st = mp_download(ctx, coll_cost, dco, K * S))) return st;
-  if ((st = mp_download(ctx, coll_feas, dcf, K * S))) return st;
+  if ((st = mp_download(ctx, U_out, d.U, 2 * H * S))) return st;
+  if ((st = mp_download(ctx, traj_out, d.traj, (H + 1) * 7 * S))) return st;
+  if ((st = mp_download(ctx, cost_out, d.cost, (size_t)S))) return st;
+  if ((st = mp_download(ctx, feasible_out, d.feasible, (size_t)S))) return st;
+  if ((st = mp_download(ctx, rollout_count_out, d.rc, (size_t)S))) return st;
+  if ((st = mp_download(ctx, feasible_count_out, d.fc, (size_t)S))) return st;
+  if ((st = mp_download(ctx, coll_traj, c.traj, K * (H + 1) * 7 * S))) return st;
+  if ((st = mp_download(ctx, coll_ctrl, c.ctrl, K * H * 2 * S))) return st;
+  if ((st = mp_download(ctx, coll_cost, c.cost, K * S))) return st;
+  if ((st = mp_download(ctx, coll_feas, c.feas, K * S))) return st;
   if ((st = mp_download(ctx, &flag, ctx->flags, 1))) return st;
   MP_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (flag & 1) return mp_fail(ctx, MP_ERR_NUMERIC, "NaN rollout cost (Julia would have produced NaN weights)");
@@ -1324,10 +1314,8 @@ int mp_mppi_closed_loop(mp_ctx* ctx, const mp_mppi_params* p, const mp_mppi_loop
   MP_CHECK(ctx, lp->update_steps >= 1, "update_steps (%d) must be >= 1", lp->update_steps);
   MP_CHECK(ctx, lp->max_steps >= 0, "max_steps (%d) must be >= 0", lp->max_steps);
   MP_CHECK(ctx, lp->plant_dt > 0.0, "plant_dt (%g) must be > 0", lp->plant_dt);
-  MP_CHECK(ctx, X0 && goal && U_nom0 && hold_idx && his && n_rows && n_replans, "required pointer is NULL");
-  MP_CHECK(ctx, p->noise_mode != MP_NOISE_EXTERNAL || noise, "noise is NULL in MP_NOISE_EXTERNAL mode");
-  MP_CHECK(ctx, p->n_obs == 0 || obstacles, "obstacles NULL with n_obs > 0");
-  MP_CHECK(ctx, p->grid_nx == 0 || grid, "grid NULL with grid_nx > 0");
+  const PlanIn in = {X0, goal, U_nom0, obstacles, grid, noise};
+  if ((st = check_plan_inputs(ctx, p, in, hold_idx && his && n_rows && n_replans))) return st;
   for (int i = 0; i < lp->update_steps; i++)
     MP_CHECK(ctx, hold_idx[i] >= 0 && hold_idx[i] < p->H, "hold_idx[%d] = %d outside [0, H=%d)", i, hold_idx[i],
              p->H);
@@ -1337,13 +1325,8 @@ int mp_mppi_closed_loop(mp_ctx* ctx, const mp_mppi_params* p, const mp_mppi_loop
   const size_t RR = R > 0 ? (size_t)R : 1;
   st = MP_OK;
   // device state: the plant states (= the next plan's X0), logs replan-major [R][S]...
-  double* dstate = (double*)mp_upload(ctx, WS_IO0, X0, 7 * SS, &st);
-  const double* dgoal = mp_upload(ctx, WS_IO1, goal, 2 * SS, &st);
-  const double* dU0 = mp_upload(ctx, WS_IO2, U_nom0, 2 * H * SS, &st);
-  const double* dobs = mp_upload(ctx, WS_IO3, p->n_obs ? obstacles : nullptr, 3 * (size_t)p->n_obs * SS, &st);
-  const uint8_t* dgrid = mp_upload(ctx, WS_IO4, p->grid_nx ? grid : nullptr, (size_t)p->grid_nx * p->grid_ny * SS, &st);
-  const double* dnoise =
-      mp_upload(ctx, WS_IO5, p->noise_mode == MP_NOISE_EXTERNAL ? noise : nullptr, RR * SS * K * H * 2, &st);
+  const PlanIn din = upload_scene_inputs(ctx, p, SS, in, RR * SS * K * H * 2, &st);
+  double* dstate = (double*)din.X0;  // the plant kernel advances it in place
   const int32_t* dhold = mp_upload(ctx, WS_IO15, hold_idx, nsub, &st);
   double* dU = (double*)mp_ws(ctx, WS_IO6, sizeof(double) * RR * SS * H * 2);
   const size_t traj_n = (traj_log ? RR : 1) * SS * (H + 1) * 7;  // without a log: one scratch set
@@ -1378,21 +1361,26 @@ int mp_mppi_closed_loop(mp_ctx* ctx, const mp_mppi_params* p, const mp_mppi_loop
   const int poll = lp->poll_every > 0 ? lp->poll_every : 8;
   const double r2 = lp->goal_radius * lp->goal_radius;
   int pending = -1;  // pinned half holding the last poll's live flags (its copy is in flight)
-  hipEvent_t ev_poll[2];
+  struct PollEvents {  // destroyed on every return path
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    ~PollEvents() { for (hipEvent_t e : ev) if (e) hipEventDestroy(e); }
+  } polls;
+  hipEvent_t* ev_poll = polls.ev;
   MP_HIP(ctx, hipEventCreateWithFlags(&ev_poll[0], hipEventDisableTiming));
   MP_HIP(ctx, hipEventCreateWithFlags(&ev_poll[1], hipEventDisableTiming));
   int rc = MP_OK;
   for (int r = 0; r < R; r++) {
     MppiDev Dr = D;
     Dr.offset = p->offset + (unsigned long long)r;  // a fresh Philox counter word per replan
-    const double* un = r == 0 ? dU0 : dU + (size_t)(r - 1) * SS * H * 2;  // NominalControls = r.Control
-    double* tr = dtraj + (traj_log ? (size_t)r * SS * (H + 1) * 7 : 0);
-    rc = plan_launch(ctx, Dr, S, dstate, dgoal, un, dobs, dgrid, dnoise ? dnoise + (size_t)r * SS * K * H * 2 : nullptr,
-                     dU + (size_t)r * SS * H * 2, tr, dcost + (size_t)r * SS, dfeas + (size_t)r * SS,
-                     drc + (size_t)r * SS, dfc + (size_t)r * SS, nullptr, nullptr, nullptr, nullptr, 1, live);
+    PlanIn rin = din;
+    if (r > 0) rin.U_nom = dU + (size_t)(r - 1) * SS * H * 2;  // NominalControls = r.Control
+    if (din.noise) rin.noise = din.noise + (size_t)r * SS * K * H * 2;
+    const PlanOut rout = {dU + (size_t)r * SS * H * 2, dtraj + (traj_log ? (size_t)r * SS * (H + 1) * 7 : 0),
+                          dcost + (size_t)r * SS, dfeas + (size_t)r * SS, drc + (size_t)r * SS, dfc + (size_t)r * SS};
+    rc = plan_launch(ctx, Dr, S, rin, rout, {nullptr, nullptr, nullptr, nullptr}, 1, live);
     if (rc) break;
     hipLaunchKernelGGL(loop_plant_kernel, dim3((unsigned)((2 * SS + 63) / 64)), dim3(64), 0, ctx->stream, S, (int)H,
-                       dstate, (const double*)(dU + (size_t)r * SS * H * 2), dhold, (int)nsub, lp->plant_dt, dgoal, r2,
+                       dstate, (const double*)(dU + (size_t)r * SS * H * 2), dhold, (int)nsub, lp->plant_dt, din.goal, r2,
                        (int)(r * nsub), (int)M, drows, dst, r);
     if (hipGetLastError() != hipSuccess) { rc = mp_fail(ctx, MP_ERR_HIP, "loop_plant_kernel launch failed"); break; }
     if ((r + 1) % poll == 0 && r + 1 < R) {
@@ -1415,8 +1403,6 @@ int mp_mppi_closed_loop(mp_ctx* ctx, const mp_mppi_params* p, const mp_mppi_loop
   }
   if (!rc) rc = mp_ctx_join(ctx);  // the logged final rollouts come from the side stream
   mp_sync_all(ctx);
-  hipEventDestroy(ev_poll[0]);
-  hipEventDestroy(ev_poll[1]);
   if (rc) return rc;
   // results: [S]-major host layouts
   std::vector<int32_t> hst(3 * SS);
@@ -1457,13 +1443,9 @@ int mp_mppi_plan_sharded(mp_ctx** ctxs, int32_t n, const mp_mppi_params* p, int3
   if (st) return st;
   MppiDev D;
   if ((st = make_dev_params(c0, p, p ? p->K : 0, &D))) return st;
-  MP_CHECK(c0, S >= 1, "S (%d) must be >= 1", S);
-  MP_CHECK(c0, X0 && goal && U_nom && U_out && traj_out && cost_out && feasible_out && rollout_count_out &&
-               feasible_count_out, "required pointer is NULL");
-  MP_CHECK(c0, p->noise_mode != MP_NOISE_EXTERNAL || noise, "noise is NULL in MP_NOISE_EXTERNAL mode");
-  MP_CHECK(c0, p->n_obs == 0 || obstacles, "obstacles NULL with n_obs > 0");
-  MP_CHECK(c0, p->grid_nx == 0 || grid, "grid NULL with grid_nx > 0");
-  MP_CHECK(c0, p->final_stream == 0 || p->final_stream == 1, "final_stream (%d) must be 0 or 1", p->final_stream);
+  if ((st = check_plan_call(c0, p, S, {X0, goal, U_nom, obstacles, grid, noise},
+                            {U_out, traj_out, cost_out, feasible_out, rollout_count_out, feasible_count_out})))
+    return st;
   const size_t K = p->K, H = p->H, Dr = shard_rec((int)H), gb = (size_t)p->grid_nx * p->grid_ny;
   const int base = S / n, rem = S % n, smax = base + (rem > 0);
   auto lo = [&](int r) { return r * base + (r < rem ? r : rem); };
@@ -1503,31 +1485,26 @@ int mp_mppi_plan_sharded(mp_ctx** ctxs, int32_t n, const mp_mppi_params* p, int3
     MP_SH(hipMemsetAsync(c->flags, 0, sizeof(int), c->stream));
     if (cnt == 0) continue;  // more ranks than scenes: this rank only takes part in the gather
     st = MP_OK;
-    const double* dX0 = mp_upload(c, WS_IO0, X0 + 7 * sa, 7 * sc, &st);
-    const double* dgoal = mp_upload(c, WS_IO1, goal + 2 * sa, 2 * sc, &st);
-    const double* dun = mp_upload(c, WS_IO2, U_nom + 2 * H * sa, 2 * H * sc, &st);
-    const double* dobs = mp_upload(c, WS_IO3, p->n_obs ? obstacles + 3 * (size_t)p->n_obs * sa : nullptr,
-                                   3 * (size_t)p->n_obs * sc, &st);
-    const uint8_t* dgrid = mp_upload(c, WS_IO4, gb ? grid + gb * sa : nullptr, gb * sc, &st);
-    const double* dnoise = mp_upload(c, WS_IO5, p->noise_mode == MP_NOISE_EXTERNAL ? noise + K * H * 2 * sa : nullptr,
-                                     K * H * 2 * sc, &st);
-    double* dU = (double*)mp_ws(c, WS_IO6, sizeof(double) * 2 * H * sc);
-    double* dtraj = (double*)mp_ws(c, WS_IO7, sizeof(double) * (H + 1) * 7 * sc);
-    double* dcost = (double*)mp_ws(c, WS_IO8, sizeof(double) * sc);
-    int32_t* dfe = (int32_t*)mp_ws(c, WS_IO9, sizeof(int32_t) * sc);
-    int32_t* drc = (int32_t*)mp_ws(c, WS_IO10, sizeof(int32_t) * sc);
-    int32_t* dfc = (int32_t*)mp_ws(c, WS_IO11, sizeof(int32_t) * sc);
-    if (st || !dU || !dtraj || !dcost || !dfe || !drc || !dfc)
+    auto from = [](auto* q, size_t i) { return q ? q + i : nullptr; };  // an absent input stays null
+    const PlanIn hin = {X0 + 7 * sa, goal + 2 * sa, U_nom + 2 * H * sa, from(obstacles, 3 * (size_t)p->n_obs * sa),
+                        from(grid, gb * sa), from(noise, K * H * 2 * sa)};
+    const PlanIn din = upload_scene_inputs(c, p, sc, hin, K * H * 2 * sc, &st);
+    const PlanOut d = {(double*)mp_ws(c, WS_IO6, sizeof(double) * 2 * H * sc),
+                       (double*)mp_ws(c, WS_IO7, sizeof(double) * (H + 1) * 7 * sc),
+                       (double*)mp_ws(c, WS_IO8, sizeof(double) * sc),
+                       (int32_t*)mp_ws(c, WS_IO9, sizeof(int32_t) * sc),
+                       (int32_t*)mp_ws(c, WS_IO10, sizeof(int32_t) * sc),
+                       (int32_t*)mp_ws(c, WS_IO11, sizeof(int32_t) * sc)};
+    if (st || !d.U || !d.traj || !d.cost || !d.feasible || !d.rc || !d.fc)
       return done(mp_fail(c0, st ? st : MP_ERR_NOMEM, "rank %d: %s", r, c->err.c_str()));
     MppiDev Dr_ = D;
     Dr_.scene_base = p->scene_base + a;
-    if ((st = plan_launch(c, Dr_, cnt, dX0, dgoal, dun, dobs, dgrid, dnoise, dU, dtraj, dcost, dfe, drc, dfc, nullptr,
-                          nullptr, nullptr, nullptr, p->final_stream)))
+    if ((st = plan_launch(c, Dr_, cnt, din, d, {nullptr, nullptr, nullptr, nullptr}, p->final_stream)))
       return done(mp_fail(c0, st, "rank %d: %s", r, c->err.c_str()));
     if (p->final_stream && (st = mp_ctx_join(c))) return done(mp_fail(c0, st, "rank %d: %s", r, c->err.c_str()));
     const long long tot = (long long)cnt * (long long)Dr;
     hipLaunchKernelGGL(shard_pack_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c->stream, cnt, (int)H,
-                       dU, dtraj, dcost, dfe, drc, dfc, (double*)send[r]);
+                       d.U, d.traj, d.cost, d.feasible, d.rc, d.fc, (double*)send[r]);
     MP_SH(hipGetLastError());
   }
   // the exchange step: every GPU ends with every scene's results (RCCL all-gather over xGMI)
