@@ -92,7 +92,11 @@ typedef struct mp_mppi_params {
   double CL[MP_NU], CU[MP_NU];
   double slack_penalty;      /* SlackPenalty (1e5)                              */
   double obs_penalty;        /* 100*712.5 (MPPIUtils.jl:127); DWA: 10000*712.5  */
-  int32_t grid_nx, grid_ny;  /* occupancy grid (build extension), 0 = none      */
+  int32_t grid_nx, grid_ny;  /* occupancy grid (build extension), 0 = none: after */
+                             /*   the circles, a state with fx = (x - grid_x0) / */
+                             /*   grid_dx in [0, nx), fy likewise in [0, ny) and */
+                             /*   grid[(int)fy][(int)fx] != 0 is infeasible and  */
+                             /*   costs one more obs_penalty; off the grid: free */
   double grid_x0, grid_y0, grid_dx, grid_dy;
   int32_t noise_mode;        /* MP_NOISE_*                                      */
   int32_t ctrl_cost;         /* 1: λ·u_nomᵀΣ⁻¹(u−u_nom) term (MPPIUtils.jl:45)  */
@@ -128,7 +132,9 @@ typedef struct mp_mppi_params {
  *      obstacles[S][n_obs][3]  MPPI.s.obstacle_list (defineMPPIobs!, setup.jl:61-64), may be NULL if n_obs == 0
  *      grid[S][ny][nx] uint8 occupancy (1 = occupied), NULL if grid_nx == 0
  *      noise[S][K][H][2]  standard normals z (MP_NOISE_EXTERNAL), else NULL;
- *                     control = clamp(U_nom + L z, CL, CU), L = chol(Σ).L (MPPIUtils.jl:5-20)
+ *                     control = clamp(U_nom + L z, CL, CU), L = cholesky(Σ).L as LAPACK potrf gives it
+ *                     (dpotf2: L21 = Σ21 * (1 / L11)); inv(Σ) of the control cost is getrf + getri
+ *                     (MPPIUtils.jl:5-20,45; setup.jl:57)
  * out: U_out[S][H][2]       MPPI.r.Control (= MPPICtrl)
  *      traj_out[S][H+1][7]  MPPI.r.Traj
  *      cost_out[S]          MPPI.r.cost

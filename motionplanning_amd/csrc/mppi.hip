@@ -894,7 +894,7 @@ static void inv2(const double* A, double* Ai) {
   }
   const bool swap = __builtin_fabs(c) > __builtin_fabs(a);
   const double p11 = swap ? c : a, p12 = swap ? d : b, q11 = swap ? a : c, q12 = swap ? b : d;
-  const double l = q11 / p11, u22 = q12 - l * p12;
+  const double l = q11 * (1.0 / p11), u22 = q12 - l * p12;  // dgetf2 scales by the reciprocal
   const double iu11 = 1.0 / p11, iu22 = 1.0 / u22, iu12 = -(p12 * iu11) * iu22;
   const double m11 = iu11 - iu12 * l, m12 = iu12, m21 = -iu22 * l, m22 = iu22;
   if (swap) { Ai[0] = m12; Ai[1] = m11; Ai[2] = m22; Ai[3] = m21; }
@@ -923,7 +923,7 @@ static int make_dev_params(mp_ctx* ctx, const mp_mppi_params* p, int K, MppiDev*
   const double* S = p->sigma;
   MP_CHECK(ctx, S[0] > 0.0, "Σ must be positive definite");
   const double l11 = __builtin_sqrt(S[0]);
-  const double l21 = S[2] / l11;
+  const double l21 = S[2] * (1.0 / l11);  // LAPACK potrf (dpotf2) scales by the reciprocal
   const double r22 = S[3] - l21 * l21;
   MP_CHECK(ctx, r22 > 0.0, "Σ must be positive definite");
   D->L[0] = l11; D->L[1] = 0.0; D->L[2] = l21; D->L[3] = __builtin_sqrt(r22);

@@ -4,7 +4,9 @@ ctypes access to the OpenBLAS that numpy ships (0.3.29, DYNAMIC_ARCH; SkylakeX k
 host) through its Fortran interface -- dgemm_64_ / dgemv_64_ / ddot_64_, the ILP64 entry points
 Julia's LinearAlgebra.BLAS ccalls.  It is the ground truth that pins oracle/or_blas.h (the rounding
 of the reference's BLAS-dispatched products) in tests/test_oracle_blas.py and the Julia-dispatch
-products of tools/ilqr_ulp_sources.py / tools/blas_replay.py.  Never used by the product.
+products of tools/ilqr_ulp_sources.py / tools/blas_replay.py.  Its LAPACK (dgetrf_64_ / dgetri_64_ / dpotrf_64_ /
+dtrtrs_64_, called as Julia's LAPACK.getrf! / getri! / potrf! / trtrs! call them) pins inv(Σ) and cholesky(Σ) of
+the MPPI plan in tests/test_mppi_ref.py.  Never used by the product.
 """
 import ctypes
 import glob
@@ -77,6 +79,62 @@ def gemv(A, x, t=False):
     lib().scipy_dgemv_64_(ctypes.c_char_p(b"T" if t else b"N"), _r(m), _r(n), ctypes.byref(one), _p(A), _r(m),
                           _p(x), _r(1), ctypes.byref(zero), _p(y), _r(1), ctypes.c_size_t(1))
     return y
+
+
+def getrf_getri(A):
+    """inv(A) of a general square matrix as Julia's inv!(lu(A)) gets it: LAPACK.getrf!(A) then
+    LAPACK.getri!(A, ipiv) (workspace query with lwork = -1 first, as getri! does).
+    Returns (inv(A), ipiv) with ipiv LAPACK's 1-based row interchanges."""
+    A = np.array(A, np.float64, order="F")
+    n = A.shape[0]
+    assert A.shape == (n, n)
+    ipiv = np.zeros(n, np.int64)
+    info = _i64(0)
+    pi = ipiv.ctypes.data_as(ctypes.POINTER(_i64))
+    lib().scipy_dgetrf_64_(_r(n), _r(n), _p(A), _r(max(1, n)), pi, ctypes.byref(info))
+    if info.value:
+        raise np.linalg.LinAlgError("dgetrf info = %d" % info.value)
+    work = np.zeros(1)
+    lwork = -1
+    for _ in range(2):
+        lib().scipy_dgetri_64_(_r(n), _p(A), _r(max(1, n)), pi, _p(work), _r(lwork), ctypes.byref(info))
+        if info.value:
+            raise np.linalg.LinAlgError("dgetri info = %d" % info.value)
+        if lwork < 0:
+            lwork = int(work[0])
+            work = np.zeros(max(1, lwork))
+    return np.ascontiguousarray(A), ipiv
+
+
+def potrf(A, uplo="U"):
+    """LAPACK.potrf!(uplo, A): the Cholesky factor in the `uplo` triangle (the other triangle zeroed
+    here).  Julia's cholesky(A) factors Hermitian(A, :U), i.e. potrf('U'), and .L is its transpose."""
+    A = np.array(A, np.float64, order="F")
+    n = A.shape[0]
+    assert A.shape == (n, n) and uplo in ("U", "L")
+    info = _i64(0)
+    lib().scipy_dpotrf_64_(ctypes.c_char_p(uplo.encode()), _r(n), _p(A), _r(max(1, n)), ctypes.byref(info),
+                           ctypes.c_size_t(1))
+    if info.value:
+        raise np.linalg.LinAlgError("dpotrf info = %d" % info.value)
+    return np.ascontiguousarray(np.triu(A) if uplo == "U" else np.tril(A))
+
+
+def trtrs_identity(A, uplo="U"):
+    """inv of a triangular matrix as Julia's inv(UpperTriangular(A)) / inv(LowerTriangular(A)) gets it:
+    LAPACK.trtrs!(uplo, 'N', 'N', A, Matrix(I)) -- the path Julia's inv(A) takes when istriu(A) or
+    istril(A) holds, a diagonal Σ included."""
+    A = np.array(A, np.float64, order="F")
+    n = A.shape[0]
+    B = np.asfortranarray(np.eye(n))
+    info = _i64(0)
+    c = ctypes.c_char_p
+    lib().scipy_dtrtrs_64_(c(uplo.encode()), c(b"N"), c(b"N"), _r(n), _r(n), _p(A), _r(max(1, n)), _p(B),
+                           _r(max(1, n)), ctypes.byref(info), ctypes.c_size_t(1), ctypes.c_size_t(1),
+                           ctypes.c_size_t(1))
+    if info.value:
+        raise np.linalg.LinAlgError("dtrtrs info = %d" % info.value)
+    return np.ascontiguousarray(B)
 
 
 def dot(x, y):

@@ -28,6 +28,12 @@
  *   OptimalControl/ILQR/ILQR.jl:56-66       the Riccati products (dgemm, shapes in or_ilqr.c)
  *   OptimalControl/ILQR/ILQR.jl:76          Klist*(xtilde .- xn)              dgemv 'N' 2x4
  *   OptimalControl/MPPI/src/MPPIUtils.jl:45 λ * u' * inv(Σ) * d  = ((λu')*Σ⁻¹)*d: dgemv 'T' 2x2, ddot 2
+ *
+ * The reference also reaches LAPACK, outside this header's products: inv(Σ) (MPPIUtils.jl:45) is getrf + getri,
+ * or the triangular solve trtrs for a diagonal Σ, and MvNormal's cholesky(Σ) (setup.jl:57) is potrf 'U'.
+ * or_mppi.c's or_inv2 / or_chol2 restate them for n = 2 (dgetf2 and dpotf2 scale by a reciprocal, no FMA
+ * involved) and tests/test_mppi_ref.py pins both against the same OpenBLAS build (oracle/openblas.py
+ * getrf_getri / potrf / trtrs_identity).
  */
 #ifndef OR_BLAS_H
 #define OR_BLAS_H

@@ -107,7 +107,9 @@ static double bound_eval(const mp_mppi_params* p, const double* s, int* ok) {
   return cost;
 }
 
-/* inv(Σ) for 2x2 (LU with partial pivoting, as LAPACK getrf/getri does). */
+/* inv(Σ) for 2x2 as Julia's inv gets it: a diagonal Σ through the triangular solve, otherwise LAPACK
+ * getrf (dgetf2: first largest pivot, the multiplier scaled by the reciprocal) + getri (dtrti2, then
+ * inv(U) inv(L) and the column swap).  Pinned against OpenBLAS's LAPACK by tests/test_mppi_ref.py. */
 void or_inv2(const double* A, double* Ai) {
   double a = A[0], b = A[1], c = A[2], d = A[3];
   if (b == 0.0 && c == 0.0) {
@@ -116,7 +118,7 @@ void or_inv2(const double* A, double* Ai) {
   }
   int swap = fabs(c) > fabs(a);
   double p11 = swap ? c : a, p12 = swap ? d : b, q11 = swap ? a : c, q12 = swap ? b : d;
-  double l = q11 / p11, u22 = q12 - l * p12;
+  double l = q11 * (1.0 / p11), u22 = q12 - l * p12; /* dgetf2 scales by the reciprocal */
   double iu11 = 1.0 / p11, iu22 = 1.0 / u22, iu12 = -(p12 * iu11) * iu22;
   /* inv(A) P^T = inv(U) inv(L);  inv(L) = [1 0; -l 1] */
   double m11 = iu11 - iu12 * l, m12 = iu12, m21 = -iu22 * l, m22 = iu22;
@@ -124,10 +126,11 @@ void or_inv2(const double* A, double* Ai) {
   else { Ai[0] = m11; Ai[1] = m12; Ai[2] = m21; Ai[3] = m22; }
 }
 
-/* cholesky(Σ).L, row-major [L11 0; L21 L22] */
+/* cholesky(Σ).L, row-major [L11 0; L21 L22]: LAPACK potrf 'U' (dpotf2) transposed, as Julia's
+ * cholesky(Hermitian(Σ, :U)).L; pinned against OpenBLAS's LAPACK by tests/test_mppi_ref.py. */
 void or_chol2(const double* A, double* L) {
   double l11 = sqrt(A[0]);
-  double l21 = A[2] / l11;
+  double l21 = A[2] * (1.0 / l11); /* dpotf2 scales by the reciprocal */
   double l22 = sqrt(A[3] - l21 * l21);
   L[0] = l11; L[1] = 0.0; L[2] = l21; L[3] = l22;
 }
