@@ -767,6 +767,40 @@ int mp_rs_create_path(mp_ctx* ctx, int64_t n, const double* init, const double* 
 int mp_rs_cost_matrix(mp_ctx* ctx, int32_t na, const double* a, int32_t nb, const double* b, double minR,
                       double* dist, uint8_t* best);
 
+/* ---------------------------------------------------------- Reeds-Shepp roadmap */
+/* A multi-query roadmap planner for a car (PRM under the Reeds-Shepp metric): a build extension, the reference
+ * has no such planner.  Every edge has the reference's semantics: its length d(a -> b) is mp_rs_cost_matrix's
+ * value, and it is free iff RS_connected (hybrid_astar_utils.jl:224-233) holds for the pose pair: createActPath of
+ * the winning candidate, block_collision_check at sparcity_num = 5 with the rectangle centre vehicle_len/2 ahead
+ * of the pose and ConvexCollision's && of both SATs.  A non-finite d (identical poses give NaN) is no candidate.
+ *   nodes[n][3] poses [x, y, ψ], 1 <= n <= MP_ROADMAP_MAX_NODES (a node's n distances are ranked in 32 KB of LDS);
+ *   walls[n_walls][5] blocks [x, y, ψ, l/2, w/2], any count (NULL with n_walls = 0); minR finite and > 0;
+ *   1 <= k <= MP_ROADMAP_MAX_K.
+ * Common errors, MP_ERR_INVALID with nothing written: a NULL argument, a count out of range, a non-finite pose,
+ * wall or vehicle size, minR not finite and positive.  An output above the workspace limit: MP_ERR_NOMEM. */
+#define MP_ROADMAP_MAX_NODES 4096
+#define MP_ROADMAP_MAX_K 64
+#define MP_ROADMAP_MAX_QUERIES 65535
+
+/* The directed roadmap: nbr[n][k], row i = the k nodes j != i with the smallest finite d(i -> j), ordered by
+ * (d, j) and padded with -1; w[n][k] = d where the edge is free, +Inf where it is blocked or padding. */
+int mp_roadmap_build(mp_ctx* ctx, int32_t n, const double* nodes, int32_t n_walls, const double* walls, double minR,
+                     double vehicle_len, double vehicle_wid, int32_t k, int32_t* nbr, double* w);
+
+/* B queries start[B][3] -> goal[B][3] on a roadmap (nbr, w) of the same scene, 1 <= B <= MP_ROADMAP_MAX_QUERIES.
+ * Vertices: 0 = start, 1..n = nodes, n + 1 = goal.  The start joins the k nodes nearest from it (d(start -> j)),
+ * the k nodes with the smallest d(j -> goal) join the goal, both ranked as a build ranks and edge-checked, and the
+ * direct edge start -> goal is checked unless its d is not finite.  Dijkstra in fp64: settle the unsettled vertex
+ * of smallest finite dist (lowest vertex on ties) until the goal is settled or none is left; an edge relaxes on
+ * dist[u] + w < dist[v].  The entries of a row of nbr other than -1 are distinct, as a build returns them.
+ * out: found[B], cost[B] (dist[goal], +Inf when not found), seq[B][n + 2] (the vertices from start to goal, -1 from
+ *      seq_len on), seq_len[B] (0 when not found), settled[B] (vertices settled), direct_free[B].
+ * MP_ERR_INVALID also for an entry of nbr outside -1..n-1 and a non-finite start or goal. */
+int mp_roadmap_query(mp_ctx* ctx, int32_t n, const double* nodes, int32_t n_walls, const double* walls, double minR,
+                     double vehicle_len, double vehicle_wid, int32_t k, const int32_t* nbr, const double* w, int32_t B,
+                     const double* start, const double* goal, uint8_t* found, double* cost, int32_t* seq,
+                     int32_t* seq_len, int32_t* settled, uint8_t* direct_free);
+
 /* ---------------------------------------------------------- diagnostics */
 /* Evaluate one include/mp_jlmath.h function on the device for n inputs
  * (bit-exactness check against the CPU build).  fn: 0 sin, 1 cos, 2 tan, 3 atan,

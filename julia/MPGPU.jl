@@ -954,6 +954,49 @@ function path_collision(p::CollideParams, poses::Array{Float64,3}, walls::Array{
     return (; scene_free = sf, first_pose = fp, first_wall = fw, n_hit = nh, pose_free = pf)
 end
 
+# ------------------------------------------------------ Reeds-Shepp roadmap
+"""
+    roadmap_build(nodes, walls, minR, vehicle_size, k)
+
+A roadmap under the Reeds-Shepp metric (mp_roadmap_build; a build extension, every edge is RS_connected of a pose
+pair): nodes (3, n), walls (5, n_walls).  Returns nbr (k, n), 1-based with 0 past a node's last candidate, and
+w (k, n): the edge's length where it is free, Inf where it is blocked.
+"""
+function roadmap_build(nodes::Matrix{Float64}, walls::Matrix{Float64}, minR::Float64, vehicle_size, k::Integer)
+    n = size(nodes, 2); nw = size(walls, 2)
+    nbr = zeros(Int32, k, n); w = zeros(k, n)
+    c = ctx()
+    check(GC.@preserve nodes walls nbr w ccall((:mp_roadmap_build, libmpgpu), Cint,
+        (Ptr{Cvoid}, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Float64, Float64, Float64, Int32, Ptr{Int32},
+         Ptr{Float64}),
+        c, n, nodes, nw, nw == 0 ? C_NULL : pointer(walls), minR, Float64(vehicle_size[1]), Float64(vehicle_size[2]),
+        k, nbr, w), c)
+    return nbr .+ Int32(1), w
+end
+
+"""
+    roadmap_query(nodes, walls, minR, vehicle_size, nbr, w, starts, goals)
+
+B start / goal pairs (3, B) on the roadmap `roadmap_build` returned (mp_roadmap_query).  Returns found, cost, seq
+(n + 2, B; vertices 1 = start, 2..n+1 = nodes, n + 2 = goal, 0 from seq_len on), seq_len, settled and direct_free.
+"""
+function roadmap_query(nodes::Matrix{Float64}, walls::Matrix{Float64}, minR::Float64, vehicle_size,
+                       nbr::Matrix{Int32}, w::Matrix{Float64}, starts::Matrix{Float64}, goals::Matrix{Float64})
+    n = size(nodes, 2); nw = size(walls, 2); k = size(nbr, 1); B = size(starts, 2)
+    nbr0 = nbr .- Int32(1)
+    found = zeros(UInt8, B); cost = zeros(B); seq = zeros(Int32, n + 2, B); len = zeros(Int32, B)
+    settled = zeros(Int32, B); direct = zeros(UInt8, B)
+    c = ctx()
+    out = (found, cost, seq, len, settled, direct)
+    check(GC.@preserve nodes walls nbr0 w starts goals out ccall((:mp_roadmap_query, libmpgpu), Cint,
+        (Ptr{Cvoid}, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Float64, Float64, Float64, Int32, Ptr{Int32},
+         Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32},
+         Ptr{UInt8}),
+        c, n, nodes, nw, nw == 0 ? C_NULL : pointer(walls), minR, Float64(vehicle_size[1]), Float64(vehicle_size[2]),
+        k, nbr0, w, B, starts, goals, found, cost, seq, len, settled, direct), c)
+    return (; found = found .== 0x01, cost, seq = seq .+ Int32(1), seq_len = len, settled, direct_free = direct .== 0x01)
+end
+
 # --------------------------------------------------------------------- iLQR
 struct IlqrParams
     N::Int32

@@ -1,2 +1,3 @@
 from . import collision  # noqa: F401
 from . import reeds_shepp  # noqa: F401
+from . import roadmap  # noqa: F401

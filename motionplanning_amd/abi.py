@@ -230,6 +230,8 @@ SIGNATURES = {
     "mp_rs_allpath": (ctypes.c_int, [_V, _I] + [_V] * 8),
     "mp_rs_create_path": (ctypes.c_int, [_V, ctypes.c_int64] + [_V] * 5),
     "mp_rs_cost_matrix": (ctypes.c_int, [_V, _I, _V, _I, _V, ctypes.c_double, _V, _V]),
+    "mp_roadmap_build": (ctypes.c_int, [_V, _I, _V, _I, _V] + [ctypes.c_double] * 3 + [_I, _V, _V]),
+    "mp_roadmap_query": (ctypes.c_int, [_V, _I, _V, _I, _V] + [ctypes.c_double] * 3 + [_I, _V, _V, _I] + [_V] * 8),
     "mp_math_eval": (ctypes.c_int, [_V, _I, ctypes.c_int64, _V, _V, _V]),
     "mp_pinv2_eval": (ctypes.c_int, [_V, _I, ctypes.c_int64, _V, _V, _V]),
     "mp_comm_init": (ctypes.c_int, [_V, _I]),
