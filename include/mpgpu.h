@@ -525,6 +525,53 @@ int mp_grid_plan(mp_ctx* ctx, int32_t planner, int32_t flags, int32_t B, int32_t
                  const void* obstacles, double* final_cost, int32_t* found, int32_t* pops, int32_t* n_nodes,
                  int32_t* pop_seq, int32_t* path, int32_t* path_n, double* path_length);
 
+/* ------------------------------------------------------- occupancy maps */
+#define MP_MAP_BORDER 1                   /* flags bit 0: a one-cell frame around the map counts as blocked */
+#define MP_MAP_OUT_OCCUPIED 2             /* flags bit 1 (mp_grid_inflate): write 1 = occupied, MPPI's polarity */
+#define MP_MAP_D2_NONE 2147483647         /* d2 of a map with no blocked cell (INT32_MAX) */
+#define MP_MAP_MAX_BATCH_CELLS (1 << 28)  /* B*nx*ny of one call */
+#define MP_MAP_MAX_SIDE 32768             /* nx, ny of the three distance calls: d2 fits int32, a row distance uint16 */
+
+/* Tools on the maps the grid planners and MPPI take (an extension: the reference has none of them).
+ *
+ * A map is uint8_t mask[ny][nx], the planners' convention: cell (ix, iy) (1-based) at (iy-1)*nx + ix-1, any
+ * nonzero byte = free.  d2[ny][nx] (int32) is the squared Euclidean distance, in cells, from each cell to the
+ * nearest blocked cell: 0 on a blocked cell, MP_MAP_D2_NONE everywhere on a map without one.  Cells count as
+ * square and distances are in cells, not metres.  With MP_MAP_BORDER the cells of a one-cell frame around the
+ * map (ix = 0, nx+1, iy = 0, ny+1) are blocked too: d2 <= min(ix, nx+1-ix, iy, ny+1-iy)^2 and no cell has
+ * MP_MAP_D2_NONE.  Everything is integer-exact: the outputs do not depend on the batch, the device or the
+ * algorithm.
+ *
+ * All four calls take host pointers and run on the context's stream (they return after the copy back).
+ *   B >= 1, nx, ny >= 2, nx*ny <= MP_GRID_MAX_CELLS, B*nx*ny <= MP_MAP_MAX_BATCH_CELLS; for the three distance
+ *   calls also nx, ny <= MP_MAP_MAX_SIDE (beyond it a distance along a row does not fit 16 bits, nor d2 32).
+ *   A limit exceeded, an unknown flag bit, a NULL pointer or a negative r2: MP_ERR_INVALID, nothing launched or
+ *   written.  A workspace that cannot be had (mp_ctx_set_workspace_limit, or the device is full): MP_ERR_NOMEM,
+ *   nothing launched or written.  Workspaces per cell of the batch: mp_grid_distance 7 bytes, mp_grid_inflate
+ *   4, mp_grid_path_clearance 7 beside the paths.
+ *
+ * mp_grid_rasterize: the masks mp_astar_plan / mp_dka_plan / mp_bfs_plan / mp_grid_plan build for themselves from
+ *   bound[B][4] and obstacles[B][n_obs][obs_kind] (3: circles [x, y, r]; 5: blocks [x, y, psi, l/2, w/2], A*'s
+ *   checkObsSafety), byte for byte (0 / 1).  n_obs = 0 (obstacles may be NULL): every cell free.
+ * mp_grid_distance: d2[B][ny][nx] of mask[B][ny][nx].  flags: MP_MAP_BORDER.
+ * mp_grid_inflate: mask_out[B][ny][nx], 1 = free iff the cell is free in mask and d2 > r2[b] (r2 >= 0, one per
+ *   map; r2 = 0 returns mask normalised to 0 / 1; a disc of radius r cells is r2 = floor(r^2)).  With
+ *   MP_MAP_OUT_OCCUPIED the bytes are inverted, 1 = occupied (mp_mppi_plan's grid).  d2 is never written out: the
+ *   search for the nearest blocked cell stops where the verdict is known.  flags: MP_MAP_BORDER,
+ *   MP_MAP_OUT_OCCUPIED.
+ * mp_grid_path_clearance: path[B][stride] holds paths as mp_grid_plan writes them (stride >= 1), Encode values
+ *   1..nx*ny; only the first path_n[b] (0 .. stride) entries are read, an entry of 0 (a start off the map) is
+ *   skipped, any other entry outside 1..nx*ny is MP_ERR_INVALID.  min_d2[b] is the least d2 of map b over the
+ *   path's cells, at[b] the (0-based) index of the first entry that attains it; an empty path, or one skipped
+ *   entirely: MP_MAP_D2_NONE and -1.  flags: MP_MAP_BORDER. */
+int mp_grid_rasterize(mp_ctx* ctx, int32_t B, int32_t nx, int32_t ny, const double* bound, int32_t obs_kind,
+                      int32_t n_obs, const double* obstacles, uint8_t* mask);
+int mp_grid_distance(mp_ctx* ctx, int32_t flags, int32_t B, int32_t nx, int32_t ny, const uint8_t* mask, int32_t* d2);
+int mp_grid_inflate(mp_ctx* ctx, int32_t flags, int32_t B, int32_t nx, int32_t ny, const uint8_t* mask,
+                    const int32_t* r2, uint8_t* mask_out);
+int mp_grid_path_clearance(mp_ctx* ctx, int32_t flags, int32_t B, int32_t nx, int32_t ny, const uint8_t* mask,
+                           const int32_t* path, const int32_t* path_n, int32_t stride, int32_t* min_d2, int32_t* at);
+
 /* ----------------------------------------------------------- RRT / RRT* */
 #define MP_RRT_MAX_ITER 1000000 /* cap on n_iter (the tree workspace is 48 bytes per node and scene; 64 for mp_rrtnh_plan) */
 

@@ -30,7 +30,7 @@ using Interpolations: interpolate, Gridded, Constant, Previous, linear_interpola
 
 export MPPIPlan, MPPIClosedLoop, planHybridAstar!, mppi_plan_batch, mppi_plan_sharded, comm_init, mppi_closed_loop_batch,
        rollout_batch, ha_expand, ha_rs_connect, ha_astar_table, astar_plan_batch, dka_plan_batch, bfs_plan_batch, grid_plan_batch, rrt_plan_batch, rrtnh_plan_batch,
-       ha_allpath, ha_neighbor_origin, retrieve_batch!, track_batch!, ilqr_rollout, ilqr_backward!, ilqr_forward!,
+       grid_rasterize, grid_distance, grid_inflate, grid_path_clearance, ha_allpath, ha_neighbor_origin, retrieve_batch!, track_batch!, ilqr_rollout, ilqr_backward!, ilqr_forward!,
        ilqr_solve!, vehicle_euler!, ctx_join, rs_allpath, rs_create_path, rs_cost_matrix, changeBasis, allpath,
        createPath, createActPath
 
@@ -585,6 +585,81 @@ function grid_plan_batch(planner, mapbound, bound::Matrix{Float64}, start_real::
         !masked && n_obs == 0 ? C_NULL : pointer(obstacles), cost, found, pops, nn, seq, path, pn, plen), c)
     return (; final_cost = cost, found, loop_count = pops, n_nodes = nn, pop_sequence = seq, path, path_n = pn,
             path_length = plen)
+end
+
+const MP_MAP_BORDER = Int32(1)
+const MP_MAP_OUT_OCCUPIED = Int32(2)
+const MP_MAP_D2_NONE = typemax(Int32)
+
+"""
+    grid_rasterize(mapbound, bound, obstacles)
+
+The free-cell masks (nx, ny, B), UInt8 0 / 1, that the grid planners build from bound (4, B) and obstacles
+(3 or 5, n_obs, B) (mp_grid_rasterize); n_obs = 0 gives all-free masks.
+"""
+function grid_rasterize(mapbound, bound::Matrix{Float64}, obstacles::Array{Float64,3})
+    nx, ny = Int(mapbound[1]), Int(mapbound[2]); B = size(bound, 2)
+    kind = size(obstacles, 1); n_obs = size(obstacles, 2)
+    mask = zeros(UInt8, nx, ny, B)
+    c = ctx()
+    check(GC.@preserve bound obstacles mask ccall((:mp_grid_rasterize, libmpgpu), Cint,
+        (Ptr{Cvoid}, Int32, Int32, Int32, Ptr{Float64}, Int32, Int32, Ptr{Float64}, Ptr{UInt8}),
+        c, B, nx, ny, bound, kind, n_obs, n_obs == 0 ? C_NULL : pointer(obstacles), mask), c)
+    return mask
+end
+
+"""
+    grid_distance(mask; border = false)
+
+Int32 (nx, ny, B): the squared Euclidean distance, in cells, from each cell of the free-cell masks (nx, ny, B)
+(nonzero = free) to the nearest blocked cell, MP_MAP_D2_NONE on a map without one (mp_grid_distance).  border
+counts a one-cell frame around the map as blocked.
+"""
+function grid_distance(mask::Array{UInt8,3}; border = false)
+    nx, ny, B = size(mask)
+    d2 = zeros(Int32, nx, ny, B)
+    c = ctx()
+    check(GC.@preserve mask d2 ccall((:mp_grid_distance, libmpgpu), Cint,
+        (Ptr{Cvoid}, Int32, Int32, Int32, Int32, Ptr{UInt8}, Ptr{Int32}),
+        c, border ? MP_MAP_BORDER : Int32(0), B, nx, ny, mask, d2), c)
+    return d2
+end
+
+"""
+    grid_inflate(mask, r2; border = false, occupied = false)
+
+The masks with their blocked cells grown: 1 = free iff the cell is free and its squared distance exceeds r2[b]
+(mp_grid_inflate; a disc of radius r cells is r2 = floor(r^2)).  occupied writes 1 = occupied, the grid mppi_plan
+takes.
+"""
+function grid_inflate(mask::Array{UInt8,3}, r2::Vector{Int32}; border = false, occupied = false)
+    nx, ny, B = size(mask)
+    length(r2) == B || error("grid_inflate: one r2 per map")
+    out = zeros(UInt8, nx, ny, B)
+    flags = (border ? MP_MAP_BORDER : Int32(0)) | (occupied ? MP_MAP_OUT_OCCUPIED : Int32(0))
+    c = ctx()
+    check(GC.@preserve mask r2 out ccall((:mp_grid_inflate, libmpgpu), Cint,
+        (Ptr{Cvoid}, Int32, Int32, Int32, Int32, Ptr{UInt8}, Ptr{Int32}, Ptr{UInt8}),
+        c, flags, B, nx, ny, mask, r2, out), c)
+    return out
+end
+
+"""
+    grid_path_clearance(mask, path, path_n; border = false)
+
+(min_d2, at) of the paths grid_plan_batch returns (path (stride, B), path_n (B)) over the masks (nx, ny, B): the
+least squared distance to a blocked cell along each path and the 0-based index of the first entry that attains
+it; (MP_MAP_D2_NONE, -1) for an empty path (mp_grid_path_clearance).
+"""
+function grid_path_clearance(mask::Array{UInt8,3}, path::Matrix{Int32}, path_n::Vector{Int32}; border = false)
+    nx, ny, B = size(mask)
+    size(path, 2) == B && length(path_n) == B || error("grid_path_clearance: one path per map")
+    min_d2 = zeros(Int32, B); at = zeros(Int32, B)
+    c = ctx()
+    check(GC.@preserve mask path path_n min_d2 at ccall((:mp_grid_path_clearance, libmpgpu), Cint,
+        (Ptr{Cvoid}, Int32, Int32, Int32, Int32, Ptr{UInt8}, Ptr{Int32}, Ptr{Int32}, Int32, Ptr{Int32}, Ptr{Int32}),
+        c, border ? MP_MAP_BORDER : Int32(0), B, nx, ny, mask, path, path_n, size(path, 1), min_d2, at), c)
+    return (; min_d2, at)
 end
 
 struct RrtParams    # mp_rrt_params (PathPlanning/RRT/src/types.jl:19-39)

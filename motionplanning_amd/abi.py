@@ -172,6 +172,12 @@ MP_SAT_BOTH = 0
 MP_SAT_EITHER = 1
 MP_SAT_BASE_A = 2
 
+MP_MAP_BORDER = 1
+MP_MAP_OUT_OCCUPIED = 2
+MP_MAP_D2_NONE = 2147483647
+MP_MAP_MAX_BATCH_CELLS = 1 << 28
+MP_MAP_MAX_SIDE = 32768
+
 MP_TRACK_DONE = 0
 MP_TRACK_MAXSTEP = 1
 MP_TRACK_NOPATH = 2
@@ -220,6 +226,10 @@ SIGNATURES = {
     "mp_dka_plan": (ctypes.c_int, [_V, _I, _I, _I, _V, _V, _V, _I] + [_V] * 9),
     "mp_bfs_plan": (ctypes.c_int, [_V, _I, _I, _I, _V, _V, _V, _I] + [_V] * 8),
     "mp_grid_plan": (ctypes.c_int, [_V, _I, _I, _I, _I, _I, _V, _V, _V, _I, _I] + [_V] * 9),
+    "mp_grid_rasterize": (ctypes.c_int, [_V, _I, _I, _I, _V, _I, _I, _V, _V]),
+    "mp_grid_distance": (ctypes.c_int, [_V, _I, _I, _I, _I, _V, _V]),
+    "mp_grid_inflate": (ctypes.c_int, [_V, _I, _I, _I, _I, _V, _V, _V]),
+    "mp_grid_path_clearance": (ctypes.c_int, [_V, _I, _I, _I, _I, _V, _V, _V, _I, _V, _V]),
     "mp_rrt_plan": (ctypes.c_int, [_V, ctypes.POINTER(RRTParams), _I, _V, _V, _V, _I] + [_V] * 13),
     "mp_rrtnh_plan": (ctypes.c_int, [_V, ctypes.POINTER(RRTParams), _I, _V, _V, _V, _I] + [_V] * 13),
     "mp_ha_retrieve_path": (ctypes.c_int, [_V, _I, _V, _V, _V, _I] + [_V] * 8),

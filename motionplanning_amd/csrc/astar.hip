@@ -619,6 +619,53 @@ int mp_grid_plan(mp_ctx* ctx, int32_t planner, int32_t flags, int32_t B, int32_t
                  MP_GRID_MAX_CELLS, (flags & MP_GRID_FORCE_GLOBAL) != 0);
 }
 
+// the masks as_launch builds for a planner call with the same bound and obstacle list, copied out
+int mp_grid_rasterize(mp_ctx* ctx, int32_t B, int32_t nx, int32_t ny, const double* bound, int32_t obs_kind,
+                      int32_t n_obs, const double* obstacles, uint8_t* mask) {
+  if (!ctx) return MP_ERR_INVALID;
+  MP_CHECK(ctx, nx >= 2 && ny >= 2 && (long long)nx * ny <= MP_GRID_MAX_CELLS,
+           "grid %d x %d: each side must be >= 2 and nx*ny <= %d", nx, ny, MP_GRID_MAX_CELLS);
+  MP_CHECK(ctx, B >= 1 && (long long)B * nx * ny <= MP_MAP_MAX_BATCH_CELLS, "B = %d maps: B >= 1 and B*nx*ny <= %d", B,
+           MP_MAP_MAX_BATCH_CELLS);
+  MP_CHECK(ctx, bound && mask, "bound or mask is NULL");
+  MP_CHECK(ctx, obs_kind == 3 || obs_kind == 5, "obstacle kind must be 3 (circles) or 5 (blocks)");
+  MP_CHECK(ctx, n_obs >= 0 && (n_obs == 0 || obstacles) && (long long)B * n_obs <= (1 << 28), "bad obstacle list");
+  const int N = nx * ny;
+  const size_t nB = (size_t)B;
+  std::vector<double> ge(4 * nB);
+  for (int s = 0; s < B; s++)
+    MP_CHECK(ctx, as_factors(bound + 4 * (size_t)s, nx, ny, &ge[4 * s]), "bound %d must be finite", s);
+  MP_HIP(ctx, hipSetDevice(ctx->device));
+  // every workspace before the first copy or launch
+  unsigned char* dmask = (unsigned char*)mp_ws(ctx, WS_AS_MASK, nB * N);
+  if (!dmask || !mp_ws(ctx, WS_AS_GEO, sizeof(double) * 4 * nB)) return MP_ERR_NOMEM;
+  if (n_obs && (!mp_ws(ctx, WS_AS_OBS, sizeof(double) * nB * n_obs * obs_kind) ||
+                (obs_kind == 5 && !mp_ws(ctx, WS_AS_WALL, sizeof(double) * 10 * nB * n_obs))))
+    return MP_ERR_NOMEM;
+  if (n_obs == 0) {
+    MP_HIP(ctx, hipMemsetAsync(dmask, 1, nB * N, ctx->stream));
+  } else {
+    int st = MP_OK;
+    const double* geo = mp_upload(ctx, WS_AS_GEO, ge.data(), ge.size(), &st);
+    const double* dobs = mp_upload(ctx, WS_AS_OBS, obstacles, nB * n_obs * obs_kind, &st);
+    if (st || !geo || !dobs) return st ? st : MP_ERR_NOMEM;
+    double* wpts = nullptr;
+    if (obs_kind == 5) {
+      wpts = (double*)mp_ws(ctx, WS_AS_WALL, sizeof(double) * 10 * nB * n_obs);
+      hipLaunchKernelGGL(as_wall_kernel, dim3((unsigned)((B * n_obs + 63) / 64)), dim3(64), 0, ctx->stream, B * n_obs, dobs,
+                         wpts);
+      MP_HIP(ctx, hipGetLastError());
+    }
+    hipLaunchKernelGGL(as_mask_kernel, dim3((unsigned)((nB * N + 255) / 256)), dim3(256), 0, ctx->stream, B, nx, ny, geo,
+                       obs_kind, n_obs, dobs, wpts, dmask);
+    MP_HIP(ctx, hipGetLastError());
+  }
+  int st = mp_download(ctx, mask, (const uint8_t*)dmask, nB * N);
+  if (st) return st;
+  MP_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (ge outlives its upload)
+  return MP_OK;
+}
+
 int mp_ha_astar_table(mp_ctx* ctx, const mp_ha_params* p, int32_t B, const double* goal, const double* walls,
                       double* table) {
   if (!ctx) return MP_ERR_INVALID;

@@ -130,6 +130,14 @@ enum {
   WS_RRT_TREE,    // ... tree state (48 bytes per node and scene; rrtnh.hip 64)
   WS_RRT_OUT,     // ... per-scene results and paths
   WS_GB_NODE,     // large grids (gridbig.hip): the searches' node tables, 32 bytes per cell (BFS 12)
+  WS_MAP_MASK,    // occupancy maps (gridmap.hip): the caller's masks
+  WS_MAP_ROW,     // ... distance along the row to the nearest blocked cell, uint16 per cell
+  WS_MAP_D2,      // ... squared distances, int32 per cell
+  WS_MAP_OUT,     // ... inflated masks
+  WS_MAP_R2,      // ... one r2 per map
+  WS_MAP_PATH,    // ... mp_grid_path_clearance's paths
+  WS_MAP_PN,      // ... their lengths
+  WS_MAP_RES,     // ... min_d2[B] and at[B]
   WS_COUNT
 };
 
