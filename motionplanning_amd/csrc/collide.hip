@@ -32,8 +32,6 @@
 namespace {
 
 constexpr int POSE_CHUNK = 256;  // checked poses per block of collide_path_kernel, one per lane
-constexpr int WALL_TILE = 32;    // walls per LDS tile
-constexpr int WROW = 32;         // doubles per wall row: 4 corners (8) + 4 edges x [bx, by, nx, ny, min, max] (24)
 constexpr int PAIR_BLOCK = 256;  // pairs per block of collide_convex_kernel
 constexpr int CONVEX_LDS_DOUBLES = 4096;  // a scene's polygons are staged in LDS up to this many doubles (32 KiB)
 
@@ -138,7 +136,7 @@ __global__ void __launch_bounds__(POSE_CHUNK) collide_path_kernel(PathDev P, con
                                                                   unsigned long long* __restrict__ key,
                                                                   int* __restrict__ n_hit,
                                                                   unsigned char* __restrict__ pose_free) {
-  __shared__ double wt[WALL_TILE * WROW];
+  __shared__ double wt[WALL_TILE * WALL_ROW];
   __shared__ unsigned long long red_key[POSE_CHUNK / 64];
   __shared__ int red_cnt[POSE_CHUNK / 64];
   const int s = blockIdx.y, tid = threadIdx.x;
@@ -152,45 +150,25 @@ __global__ void __launch_bounds__(POSE_CHUNK) collide_path_kernel(PathDev P, con
 
   // the pose's rectangle (hybrid_astar_utils.jl:193) and its own SAT table, in registers
   double vq[8], vt[24];
-  {
-    const double* q = poses + ((size_t)s * P.n_poses + pidx) * 3;
-    const double x = q[0], y = q[1], psi = q[2];
-    double sp, cp, sy, cy;
-    mpj_sincos_bl(psi, &sp, &cp);
-    const double yaw = mpj_modpi_bl(psi);
-    mpj_sincos_bl(yaw, &sy, &cy);
-    rect_pts4(x + P.shift * cp, y + P.shift * sp, cy, sy, P.half_len, P.half_wid, vq);
-#pragma unroll
-    for (int e = 0; e < 4; e++) rect_edge(vq, e, vt + 6 * e);
-  }
+  const double* q = poses + ((size_t)s * P.n_poses + pidx) * 3;
+  vehicle_rect(q[0], q[1], q[2], P.shift, P.half_len, P.half_wid, vq, vt);
 
   int first_wall = -1;
   for (int w0 = 0; w0 < nw; w0 += WALL_TILE) {
     const int tw = min(WALL_TILE, nw - w0);
-    if (tid < tw) {  // Block2Pts of the tile's walls
+    // the tile's wall rows, built by the block (what wall_row does for one wall): corners, then edges
+    if (tid < tw) {
       const double* wl = walls + ((size_t)s * P.n_walls + w0 + tid) * 5;
       double sw, cw;
       mpj_sincos_bl(wl[2], &sw, &cw);
-      rect_pts4(wl[0], wl[1], cw, sw, wl[3], wl[4], wt + tid * WROW);
+      rect_pts4(wl[0], wl[1], cw, sw, wl[3], wl[4], wt + tid * WALL_ROW);
     }
     __syncthreads();
-    if (tid < 4 * tw) rect_edge(wt + (tid >> 2) * WROW, tid & 3, wt + (tid >> 2) * WROW + 8 + 6 * (tid & 3));
+    if (tid < 4 * tw) rect_edge(wt + (tid >> 2) * WALL_ROW, tid & 3, wt + (tid >> 2) * WALL_ROW + 8 + 6 * (tid & 3));
     __syncthreads();
     if (active && first_wall < 0) {
-      for (int w = 0; w < tw; w++) {
-        const double* row = wt + w * WROW;  // the same address in every lane: an LDS broadcast
-        // ConvexCollision(wall, vehicle), utils.jl:64-74
-        bool fr = sat_table(row + 8, vq);
-        if (P.mode == MP_SAT_BOTH) {
-          if (fr) fr = sat_table(vt, row);
-        } else if (P.mode == MP_SAT_EITHER) {
-          if (!fr) fr = sat_table(vt, row);
-        }
-        if (!fr) {
-          first_wall = w0 + w;
-          break;
-        }
-      }
+      const int w = tile_first_hit(P.mode, wt, tw, vq, vt);
+      if (w >= 0) first_wall = w0 + w;
     }
     __syncthreads();  // the tile is rebuilt next
   }
@@ -223,12 +201,6 @@ __global__ void __launch_bounds__(POSE_CHUNK) collide_path_kernel(PathDev P, con
   }
 }
 
-bool all_finite(const double* v, size_t n) {
-  for (size_t i = 0; i < n; i++)
-    if (!std::isfinite(v[i])) return false;
-  return true;
-}
-
 }  // namespace
 
 extern "C" {
@@ -239,7 +211,7 @@ int mp_block_pts(mp_ctx* ctx, int64_t n, const double* blocks, double* pts) {
   if (n == 0) return MP_OK;
   MP_CHECK(ctx, blocks && pts, "mp_block_pts: NULL argument");
   MP_CHECK(ctx, n <= (int64_t)1 << 31, "mp_block_pts: n (%lld) above 2^31", (long long)n);
-  MP_CHECK(ctx, all_finite(blocks, 5 * (size_t)n), "mp_block_pts: non-finite block");
+  MP_CHECK(ctx, mp_all_finite(blocks, 5 * (size_t)n), "mp_block_pts: non-finite block");
   int st = MP_OK;
   const double* db = mp_upload(ctx, WS_IO0, blocks, 5 * (size_t)n, &st);
   double* dp = mp_alloc_out(ctx, WS_IO1, pts, 10 * (size_t)n, &st);
@@ -259,7 +231,7 @@ static int check_polys(mp_ctx* ctx, const char* which, int B, int n, int m, cons
     MP_CHECK(ctx, c >= 2 && c <= m && c <= MP_COLLIDE_MAX_COLS,
              "mp_convex_collision: polygon %zu of %s has %d columns, outside [2, min(%d, %d)]", k, which, c, m,
              MP_COLLIDE_MAX_COLS);
-    MP_CHECK(ctx, all_finite(polys + k * m * 2, 2 * (size_t)c), "mp_convex_collision: non-finite vertex in polygon %zu of %s",
+    MP_CHECK(ctx, mp_all_finite(polys + k * m * 2, 2 * (size_t)c), "mp_convex_collision: non-finite vertex in polygon %zu of %s",
              k, which);
   }
   return MP_OK;
@@ -325,9 +297,9 @@ int mp_path_collision(mp_ctx* ctx, const mp_collide_params_t* p, int32_t B, int3
     MP_CHECK(ctx, nw >= 0 && nw <= n_walls, "mp_path_collision: wall_count[%d] = %d outside [0, %d]", b, nw, n_walls);
     const int nchk = checked_count(cnt, p->stride);
     for (int k = 0; k < nchk; k++)
-      MP_CHECK(ctx, all_finite(poses + ((size_t)b * n_poses + (size_t)k * p->stride) * 3, 3),
+      MP_CHECK(ctx, mp_all_finite(poses + ((size_t)b * n_poses + (size_t)k * p->stride) * 3, 3),
                "mp_path_collision: non-finite pose %d of scene %d", k * p->stride, b);
-    MP_CHECK(ctx, nw == 0 || all_finite(walls + (size_t)b * n_walls * 5, 5 * (size_t)nw),
+    MP_CHECK(ctx, nw == 0 || mp_all_finite(walls + (size_t)b * n_walls * 5, 5 * (size_t)nw),
              "mp_path_collision: non-finite wall in scene %d", b);
     max_chk = std::max(max_chk, nchk);
   }

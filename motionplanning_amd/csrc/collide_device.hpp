@@ -1,8 +1,11 @@
 // collide_device.hpp — the rectangle and SAT device code that collide.hip (the batched collision calls) and
 // roadmap.hip (the roadmap's fused edge check) share: GetRectanglePts, a rectangle's per-edge SAT table and
-// SeparatingAxisTheorem on it (PathPlanning/CollisionDetection/src/utils.jl), rounded as collide.hip describes.
-// Everything has internal linkage.
+// SeparatingAxisTheorem on it (PathPlanning/CollisionDetection/src/utils.jl), rounded as collide.hip describes;
+// the wall rows of an LDS tile, a checked pose's vehicle rectangle and the walk of the pose over a tile.
+// Include it after mp_jlmath.h (with MPJ_LANE_SAFE as the including file needs it).  Everything has internal linkage.
 #pragma once
+#include "../../include/mp_jlmath.h"
+#include "../../include/mpgpu.h"
 
 namespace {
 
@@ -72,6 +75,50 @@ __device__ __forceinline__ bool sat_table(const double* tab, const double* q) {
     if (edge_separates(o[0], o[1], o[2], o[3], o[4], o[5], q)) return true;
   }
   return false;
+}
+
+// ------------------------------------------------------------ walls in LDS tiles, the vehicle in registers
+// A wall's row: its 4 corners (8 doubles), then its SAT table, 4 edges x [bx, by, nx, ny, min, max] (24).
+constexpr int WALL_ROW = 32;   // doubles per wall row
+constexpr int WALL_TILE = 32;  // walls per LDS tile
+
+// Block2Pts of the wall [x, y, yaw, half length, half width] and its SAT table.
+__device__ __forceinline__ void wall_row(const double* wall5, double* row) {
+  double sw, cw;
+  mpj_sincos_bl(wall5[2], &sw, &cw);
+  rect_pts4(wall5[0], wall5[1], cw, sw, wall5[3], wall5[4], row);
+#pragma unroll
+  for (int e = 0; e < 4; e++) rect_edge(row, e, row + 8 + 6 * e);
+}
+
+// The rectangle of the vehicle at pose (x, y, ψ) (hybrid_astar_utils.jl:193), its centre `shift` ahead of the
+// pose: corners vq[8] and its own SAT table vt[24].
+__device__ __forceinline__ void vehicle_rect(double x, double y, double psi, double shift, double half_len,
+                                             double half_wid, double* vq, double* vt) {
+  double sp, cp, sy, cy;
+  mpj_sincos_bl(psi, &sp, &cp);
+  const double yaw = mpj_modpi_bl(psi);
+  mpj_sincos_bl(yaw, &sy, &cy);
+  rect_pts4(x + shift * cp, y + shift * sp, cy, sy, half_len, half_wid, vq);
+#pragma unroll
+  for (int e = 0; e < 4; e++) rect_edge(vq, e, vt + 6 * e);
+}
+
+// The first of a tile's tw wall rows that the vehicle (vq, vt) hits under `mode`, -1 if none:
+// ConvexCollision(wall, vehicle), utils.jl:64-74.
+__device__ __forceinline__ int tile_first_hit(int mode, const double* wt, int tw, const double* vq,
+                                              const double* vt) {
+  for (int w = 0; w < tw; w++) {
+    const double* row = wt + w * WALL_ROW;  // the same address in every lane: an LDS broadcast
+    bool fr = sat_table(row + 8, vq);
+    if (mode == MP_SAT_BOTH) {
+      if (fr) fr = sat_table(vt, row);
+    } else if (mode == MP_SAT_EITHER) {
+      if (!fr) fr = sat_table(vt, row);
+    }
+    if (!fr) return w;
+  }
+  return -1;
 }
 
 }  // namespace

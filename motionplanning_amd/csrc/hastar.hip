@@ -598,6 +598,8 @@ constexpr int HW_MID = 6;
 // its lanes' candidates (lane&3 = variant of the state in `s`), the per-wave winners are
 // combined in LDS in word order with the same total order (rs_before).  Every wave returns
 // the block-wide winner for its lanes; *best_id is the winning candidate id.
+// (The command rows below, in rs_known_cmd and in cmd_from_tuv are rs_cmd_write's and rs_cmd_write_tuv's of
+// rs_device.hpp written out: called through those, the ha_* kernels' register allocation and spill counts move.)
 template <bool CMD, int HWt>
 __device__ __forceinline__ double rs_best_split(const double* s, int tid, int* best_id, double* sh_c, int* sh_i,
                                                 double* cmd_out = nullptr) {
@@ -1146,7 +1148,7 @@ __global__ __launch_bounds__(64 * HWt) void ha_iter_kernel(HaDev P, IterArgs A) 
 
 
 // allpath over B normalised states: 16 states per wave, lanes 4j..4j+3 = the four variants
-// of state j; the word loop is wave-uniform.  cost[B][48], cmds[B][48][5][3], best[B].
+// of state j (rs_pair_best).  cost[B][48], cmds[B][48][5][3], best[B].
 __global__ __launch_bounds__(64) void allpath_kernel(int B, const double* __restrict__ ns, double* __restrict__ cost,
                                                      double* __restrict__ cmds, int* __restrict__ best) {
   const int lane = threadIdx.x, var = lane & 3;
@@ -1154,43 +1156,10 @@ __global__ __launch_bounds__(64) void allpath_kernel(int B, const double* __rest
   const bool live = b < B;
   double s[3] = {0.0, 0.0, 0.0};
   if (live) { s[0] = ns[3 * b]; s[1] = ns[3 * b + 1]; s[2] = ns[3 * b + 2]; }
-  double q[3];
-  rs_variant(s, var, q);
-  const RsPre R = rs_pre(q);
-  double bc = __builtin_inf();
-  int bi = 1 << 20;
-#pragma unroll 1
-  for (int w = 1; w <= 12; w++) {
-    Cmd c;
-    const double cst = rs_word(w, R, &c);
-    const int id = 4 * (w - 1) + var;
-    if (rs_before(cst, id, bc, bi)) { bc = cst; bi = id; }
-    if (live) {
-      cost[(size_t)b * 48 + id] = cst;
-      double* o = cmds + ((size_t)b * 48 + id) * 15;
-      const int n = cst < __builtin_inf() ? c.n : 0;
-#pragma unroll
-      for (int r = 0; r < 5; r++) {
-        double tr = 0.0, ge = 0.0, st = 0.0;
-        if (r < n) {
-          tr = c.tr[r];
-          ge = c.ge[r];
-          st = c.st[r];
-          if (var == 1 || var == 3) ge = -1 * ge;
-          if (var == 2 || var == 3) st = -1 * st;
-        }
-        o[3 * r] = tr;
-        o[3 * r + 1] = ge;
-        o[3 * r + 2] = st;
-      }
-    }
-  }
-#pragma unroll
-  for (int o = 2; o >= 1; o >>= 1) {
-    const double ov = __shfl_xor(bc, o);
-    const int oi = __shfl_xor(bi, o);
-    if (rs_before(ov, oi, bc, bi)) { bc = ov; bi = oi; }
-  }
+  const size_t o = (size_t)(live ? b : 0) * 48;
+  double bc;
+  int bi;
+  rs_pair_best<true, false>(s, var, live, cost + o, cmds + o * 15, &bc, &bi, nullptr);
   if (live && var == 0) best[b] = bi;
 }
 

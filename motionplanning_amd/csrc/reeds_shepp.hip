@@ -2,13 +2,14 @@
 // src/ReedsSheppsUtils.jl; rs_heuristic of HybridAstar/src/hybrid_astar_utils.jl:361-373) + C-ABI.
 //
 // rs_allpath_kernel  changeBasis + allpath + findmin for B pose pairs: 16 pairs per wave, lanes 4j..4j+3 = the four
-//                    variants of pair j, the word loop wave-uniform (allpath_kernel of hastar.hip with the
-//                    changeBasis prologue; the norm and command stores are optional).
+//                    variants of pair j, the word loop wave-uniform (rs_pair_best of rs_device.hpp); the norm and
+//                    command stores are optional.
 // rs_matrix_kernel   the Reeds–Shepp distance of every (a_i, b_j): the same lane layout, a wave's 16 pairs along b,
 //                    no command stores (8 B + 1 optional byte per pair), sin/cos of a_i's heading once per block.
 // rs_path_kernel     createPath / createActPath for n command tables: a block takes RS_PT paths segment by segment --
 //                    the heading recurrence and the x / y running sums one lane per chain, the 100 sincos and
-//                    increments of a segment one thread per (path, step), turned through LDS in between.
+//                    increments of a segment one thread per (path, step), turned through LDS in between (the three
+//                    chains are rs_device.hpp's).
 #include <cstdint>
 
 // the libm routines run under divergent control flow here (tails, ragged tiles): lane-safe variants
@@ -22,56 +23,7 @@ namespace {
 constexpr int RS_NCAND = 48;
 constexpr int RS_MAXPATH = 501;  // 100 * 5 segments + 1
 constexpr int RS_MT = 256;       // rs_matrix_kernel: threads per block = 64 pairs along b
-constexpr int RS_PT = 16;        // rs_path_kernel: paths per block
-constexpr int RS_PTH = 256;      // ... threads per block
-constexpr int RS_PST = 101;      // ... LDS row stride in doubles (100 steps + 1: ψ_0..ψ_100; odd against bank conflicts)
-
-// The word loop of allpath for this lane's variant of normalised state s: the winner among its twelve candidates in
-// (bc, bi); cost (this pair's [48], may be null) and, when WC, cmds ([48][5][3]) are written when `live`.
-template <bool WC>
-__device__ __forceinline__ void rs_words(const double* s, int var, bool live, double* __restrict__ cost,
-                                         double* __restrict__ cmds, double* bc_out, int* bi_out) {
-  double q[3];
-  rs_variant(s, var, q);
-  const RsPre R = rs_pre(q);
-  double bc = __builtin_inf();
-  int bi = 1 << 20;
-#pragma unroll 1
-  for (int w = 1; w <= 12; w++) {
-    Cmd c;
-    const double cst = rs_word(w, R, WC ? &c : nullptr);
-    const int id = 4 * (w - 1) + var;
-    if (rs_before(cst, id, bc, bi)) { bc = cst; bi = id; }
-    if (live && cost) cost[id] = cst;
-    if (WC && live) {
-      double* o = cmds + id * 15;
-      const int n = cst < __builtin_inf() ? c.n : 0;
-#pragma unroll
-      for (int r = 0; r < 5; r++) {
-        double tr = 0.0, ge = 0.0, st = 0.0;
-        if (r < n) {
-          tr = c.tr[r];
-          ge = c.ge[r];
-          st = c.st[r];
-          if (var == 1 || var == 3) ge = -1 * ge;
-          if (var == 2 || var == 3) st = -1 * st;
-        }
-        o[3 * r] = tr;
-        o[3 * r + 1] = ge;
-        o[3 * r + 2] = st;
-      }
-    }
-  }
-  // findmin across the four variants of the pair (rs_before is a total order)
-#pragma unroll
-  for (int o = 2; o >= 1; o >>= 1) {
-    const double ov = __shfl_xor(bc, o);
-    const int oi = __shfl_xor(bi, o);
-    if (rs_before(ov, oi, bc, bi)) { bc = ov; bi = oi; }
-  }
-  *bc_out = bc;
-  *bi_out = bi;
-}
+constexpr int RS_PTH = 256;      // rs_path_kernel: threads per block (RS_PT paths, rs_device.hpp)
 
 // main.jl:15-17 for B pose pairs.  norm may be null; cmds is written when WC.
 template <bool WC>
@@ -96,8 +48,8 @@ __global__ __launch_bounds__(64) void rs_allpath_kernel(int B, const double* __r
   }
   double bc;
   int bi;
-  rs_words<WC>(s, var, live, cost + (size_t)(live ? b : 0) * RS_NCAND,
-               WC ? cmds + (size_t)(live ? b : 0) * RS_NCAND * 15 : nullptr, &bc, &bi);
+  rs_pair_best<WC, false>(s, var, live, cost + (size_t)(live ? b : 0) * RS_NCAND,
+                          WC ? cmds + (size_t)(live ? b : 0) * RS_NCAND * 15 : nullptr, &bc, &bi, nullptr);
   if (live && var == 0) {
     best[b] = bi;
     act_cost[b] = bc * mr;
@@ -126,7 +78,7 @@ __global__ __launch_bounds__(RS_MT) void rs_matrix_kernel(int na, int nb, int nc
     }
     double bc;
     int bi;
-    rs_words<false>(s, var, false, nullptr, nullptr, &bc, &bi);
+    rs_pair_best<false, false>(s, var, false, nullptr, nullptr, &bc, &bi, nullptr);
     if (live && var == 0) {
       const size_t o = (size_t)i * nb + j;
       dist[o] = bc * minR;
@@ -141,9 +93,9 @@ __global__ __launch_bounds__(RS_MT) void rs_matrix_kernel(int na, int nb, int nc
 //            lane 2p+c of wave 1: the running sum x (c = 0) / y (c = 1) of segment s-1, in place over its increments;
 //   phase B  thread per (path, step k): stores x, y of column 100(s-1)+k+1, then sincos(ψ_k) and the increments
 //            ((gear*cos ψ)*minR)*Δt, ((gear*sin ψ)*minR)*Δt of segment s into the same slot, and stores ψ_{k+1}.
-// The three chains stay serial and in order (the bits of the reference); a path with fewer segments sits out the
-// later rounds.  Consecutive threads hold consecutive steps of a path, so a wave's stores cover one contiguous piece
-// of the path's row.  The closed form of repeated addition (mpj_rep_add_ok) is not used here: see DESIGN.md.
+// The three chains (rs_heading_chain, rs_running_sum, rs_step_inc) stay serial and in order; a path with fewer
+// segments sits out the later rounds.  Consecutive threads hold consecutive steps of a path, so a wave's stores cover
+// one contiguous piece of the path's row.
 __global__ __launch_bounds__(RS_PTH) void rs_path_kernel(long long n, const double* __restrict__ init,
                                                          const double* __restrict__ minR,
                                                          const double* __restrict__ cmds, double* __restrict__ path,
@@ -189,36 +141,11 @@ __global__ __launch_bounds__(RS_PTH) void rs_path_kernel(long long n, const doub
     // ---- phase A: the serial chains, one lane each
     if (tid < RS_PT) {
       const int p = tid;
-      if (s < nseg_s[p]) {
-        const double* cm = cmds + (size_t)(p0 + p) * 15 + 3 * s;
-        const double dt = __builtin_fabs(cm[0]) / 100;
-        const double c = (cm[2] * cm[1]) * dt;
-        double q = cur_s[p][2];
-        psi_s[p][0] = q;
-        for (int k = 0; k < 100; k++) {
-          q = q + c;
-          psi_s[p][k + 1] = q;
-        }
-        cur_s[p][2] = q;
-      }
+      if (s < nseg_s[p])
+        cur_s[p][2] = rs_heading_chain(cmds + (size_t)(p0 + p) * 15 + 3 * s, cur_s[p][2], psi_s[p]);
     } else if (tid >= 64 && tid < 64 + 2 * RS_PT) {
       const int p = (tid - 64) >> 1, c = (tid - 64) & 1;
-      if (s >= 1 && s - 1 < nseg_s[p]) {
-        double* inc = c == 0 ? xs_s[p] : ys_s[p];
-        double acc = cur_s[p][c];
-        // batches of 20 increments into registers first, so the LDS reads pipeline ahead of the chain
-        for (int u0 = 0; u0 < 100; u0 += 20) {
-          double v[20];
-#pragma unroll
-          for (int u = 0; u < 20; u++) v[u] = inc[u0 + u];
-#pragma unroll
-          for (int u = 0; u < 20; u++) {
-            acc = acc + v[u];
-            inc[u0 + u] = acc;
-          }
-        }
-        cur_s[p][c] = acc;
-      }
+      if (s >= 1 && s - 1 < nseg_s[p]) cur_s[p][c] = rs_running_sum(c == 0 ? xs_s[p] : ys_s[p], cur_s[p][c]);
     }
     __syncthreads();
     // ---- phase B: one thread per (path, step)
@@ -232,15 +159,7 @@ __global__ __launch_bounds__(RS_PTH) void rs_path_kernel(long long n, const doub
         o[1] = ys_s[p][k];
       }
       if (s < ns) {
-        const double* cm = cmds + (size_t)(p0 + p) * 15 + 3 * s;
-        const double dt = __builtin_fabs(cm[0]) / 100, v = cm[1], mr = mr_s[p];
-        double sn, cs;
-        mpj_sincos_bl(psi_s[p][k], &sn, &cs);
-        double d0 = v * cs, d1 = v * sn;
-        d0 = d0 * mr;
-        d1 = d1 * mr;
-        xs_s[p][k] = d0 * dt;
-        ys_s[p][k] = d1 * dt;
+        rs_step_inc(cmds + (size_t)(p0 + p) * 15 + 3 * s, psi_s[p][k], mr_s[p], &xs_s[p][k], &ys_s[p][k]);
         row[3 * (100 * s + k + 1) + 2] = psi_s[p][k + 1];
       }
     }

@@ -3,16 +3,16 @@
 // distance is rs_heuristic's opt_cost*minR (:361-373); the graph layer on top has no counterpart in the reference.
 //
 // rm_wall_kernel      Block2Pts of the scene's walls and each wall's SAT table, once per call: wtab[n_walls][32]
-//                     (4 corners + 4 edges x [bx, by, nx, ny, min, max], collide_path_kernel's LDS row).
-// rm_rank_kernel      block per row: the row's n distances (lanes 4j..4j+3 = the four variants of column j, as
-//                     rs_matrix_kernel) stay in LDS, then k block-wide argmins on (d, j) pick the candidates in rank
+//                     (wall_row of collide_device.hpp).
+// rm_rank_kernel      block per row: the row's n distances (lanes 4j..4j+3 = the four variants of column j,
+//                     rs_pair_best) stay in LDS, then k block-wide argmins on (d, j) pick the candidates in rank
 //                     order.  mode 0 ranks d(row -> j), mode 1 d(j -> row) (the goal's columns: changeBasis is not
 //                     symmetric bit for bit).  It also writes the candidates as a pair list for rm_connect_kernel.
-// rm_connect_kernel   RS_connected for a pair list, RM_PT pairs per block: wave 0 finds each pair's winner and rebuilds
-//                     its command table from (word, variant, t, u, v); then rs_path_kernel's phases with the path in
-//                     LDS only -- the serial ψ / x / y chains one lane each, the 100 sincos and increments of a segment
+// rm_connect_kernel   RS_connected for a pair list, RS_PT pairs per block: wave 0 finds each pair's winner and rebuilds
+//                     its command table from (word, variant, t, u, v); then createPath's chains with the path in LDS
+//                     only -- the serial ψ / x / y chains one lane each, the 100 sincos and increments of a segment
 //                     one thread per (path, step) -- and after each segment's running sums land, its 20 columns
-//                     = 0 (mod 5) are tested against the walls (LDS tiles of RM_WT rows of wtab).  A hit pair sits out
+//                     = 0 (mod 5) are tested against the walls (LDS tiles of WALL_TILE rows of wtab).  A hit pair sits out
 //                     the later segments.  One double per pair leaves the kernel: d where free, +Inf where blocked.
 // rm_dijkstra_kernel  block per query over vertices 0 = start, 1..n = nodes, n + 1 = goal: dist, parent and the settled
 //                     flags in LDS, per round a block-wide argmin on (dist, vertex), then one thread per out-edge.
@@ -31,12 +31,10 @@ namespace {
 
 constexpr int RM_MAXN = MP_ROADMAP_MAX_NODES;
 constexpr int RM_RT = 256;    // rm_rank_kernel: threads per block = 64 columns per tile
-constexpr int RM_PT = 16;     // rm_connect_kernel: pairs per block
-constexpr int RM_CT = 320;    // ... threads per block: RM_PT * RM_NCHK checked poses, 5 passes over RM_PT * 100 steps
-constexpr int RM_PST = 101;   // ... LDS row stride in doubles (ψ_0..ψ_100; odd against bank conflicts)
+// rm_connect_kernel: RS_PT pairs per block in LDS rows of RS_PST (rs_device.hpp), walls in tiles of WALL_TILE rows of
+// WALL_ROW doubles (collide_device.hpp)
+constexpr int RM_CT = 320;    // ... threads per block: RS_PT * RM_NCHK checked poses, 5 passes over RS_PT * 100 steps
 constexpr int RM_NCHK = 20;   // ... checked columns per segment: steps 4, 9, ..., 99 are path columns = 0 (mod 5)
-constexpr int RM_WT = 32;     // ... walls per LDS tile
-constexpr int RM_WROW = 32;   // doubles per wall row of wtab
 constexpr int RM_DT = 256;    // rm_dijkstra_kernel: threads per block
 
 __device__ __forceinline__ bool rm_finite(double d) { return __builtin_fabs(d) < __builtin_inf(); }
@@ -65,63 +63,16 @@ __device__ __forceinline__ void block_argmin(double& d, int& i, double* red_d, i
   }
 }
 
-// allpath + findmin for this lane's variant of normalised state s (lanes 4j..4j+3 of a wave hold one pair): the
-// winner's cost and id in the pair's four lanes and, when TUV, its word's (t, u, v).  This is rs_words of
-// reeds_shepp.hip with the winner's three lengths carried through the reduction in place of its stores.
-template <bool TUV>
-__device__ __forceinline__ void rm_best(const double* s, int var, double* bc_out, int* bi_out, double* tuv_out) {
-  double q[3];
-  rs_variant(s, var, q);
-  const RsPre R = rs_pre(q);
-  double bc = __builtin_inf();
-  int bi = 1 << 20;
-  double bt[3] = {0.0, 0.0, 0.0};
-#pragma unroll 1
-  for (int w = 1; w <= 12; w++) {
-    double tv[3];
-    const double cst = rs_word(w, R, nullptr, TUV ? tv : nullptr);
-    const int id = 4 * (w - 1) + var;
-    if (rs_before(cst, id, bc, bi)) {
-      bc = cst;
-      bi = id;
-      if (TUV) { bt[0] = tv[0]; bt[1] = tv[1]; bt[2] = tv[2]; }
-    }
-  }
-#pragma unroll
-  for (int o = 2; o >= 1; o >>= 1) {
-    const double ov = __shfl_xor(bc, o);
-    const int oi = __shfl_xor(bi, o);
-    double ot[3] = {0.0, 0.0, 0.0};
-    if (TUV) {
-      ot[0] = __shfl_xor(bt[0], o);
-      ot[1] = __shfl_xor(bt[1], o);
-      ot[2] = __shfl_xor(bt[2], o);
-    }
-    if (rs_before(ov, oi, bc, bi)) {
-      bc = ov;
-      bi = oi;
-      if (TUV) { bt[0] = ot[0]; bt[1] = ot[1]; bt[2] = ot[2]; }
-    }
-  }
-  *bc_out = bc;
-  *bi_out = bi;
-  if (TUV) { tuv_out[0] = bt[0]; tuv_out[1] = bt[1]; tuv_out[2] = bt[2]; }
-}
-
 // -------------------------------------------------------------------- walls
 __global__ __launch_bounds__(64) void rm_wall_kernel(int nw, const double* __restrict__ walls,
                                                      double* __restrict__ wtab) {
   const int i = blockIdx.x * 64 + threadIdx.x;
   if (i >= nw) return;
-  const double* wl = walls + 5 * (size_t)i;
-  double row[RM_WROW], sw, cw;
-  mpj_sincos_bl(wl[2], &sw, &cw);
-  rect_pts4(wl[0], wl[1], cw, sw, wl[3], wl[4], row);
+  double row[WALL_ROW];
+  wall_row(walls + 5 * (size_t)i, row);
+  double* o = wtab + (size_t)i * WALL_ROW;
 #pragma unroll
-  for (int e = 0; e < 4; e++) rect_edge(row, e, row + 8 + 6 * e);
-  double* o = wtab + (size_t)i * RM_WROW;
-#pragma unroll
-  for (int j = 0; j < RM_WROW; j++) o[j] = row[j];
+  for (int j = 0; j < WALL_ROW; j++) o[j] = row[j];
 }
 
 // -------------------------------------------------------------------- candidates
@@ -152,7 +103,7 @@ __global__ __launch_bounds__(RM_RT) void rm_rank_kernel(int n, int k, int mode, 
     }
     double bc;
     int bi;
-    rm_best<false>(s, var, &bc, &bi, nullptr);
+    rs_pair_best<false, false>(s, var, false, nullptr, nullptr, &bc, &bi, nullptr);
     if (live && var == 0) {
       const double d = bc * minR;
       d_s[j] = (rm_finite(d) && !(excl_self && j == r)) ? d : __builtin_inf();
@@ -180,28 +131,8 @@ __global__ __launch_bounds__(RM_RT) void rm_rank_kernel(int n, int k, int mode, 
 }
 
 // -------------------------------------------------------------------- edges
-// The winner's command table [5][3] from its id and (t, u, v) (rs_word's table rows, allpath's variant signs).
-__device__ __forceinline__ void rm_cmd(int id, int n, const double* tuv, double* cmd) {
-  const int wi = id >> 2, var = id & 3;
-#pragma unroll
-  for (int r = 0; r < 5; r++) {
-    double tr = 0.0, ge = 0.0, st = 0.0;
-    if (r < n) {
-      const int code = kRsTr[wi][r];
-      tr = code == 0 ? tuv[0] : code == 1 ? tuv[1] : code == 2 ? tuv[2] : PI2;
-      ge = kRsGe[wi][r];
-      st = kRsSt[wi][r];
-      if (var == 1 || var == 3) ge = -1 * ge;
-      if (var == 2 || var == 3) st = -1 * st;
-    }
-    cmd[3 * r] = tr;
-    cmd[3 * r + 1] = ge;
-    cmd[3 * r + 2] = st;
-  }
-}
-
 // w_out[e] = d(P[pa[e]] -> P[pb[e]]) where RS_connected holds, +Inf where the path hits a wall, where d is not finite
-// or where the pair is padding (an index < 0).  Per segment s (rs_path_kernel's phases, the check between them):
+// or where the pair is padding (an index < 0).  Per segment s (createPath's chains of rs_device.hpp, the check between):
 //   A  lane p of wave 0: the heading chain of segment s; lane 2p+c of wave 1: the x / y running sum of segment s-1;
 //   C  thread (p, c): column 100(s-1) + 5c + 5 of path p (x, y from the sums, ψ saved by B of the round before)
 //      against every wall, ConvexCollision(wall, vehicle) with both SATs; s = 0: thread p, the start pose;
@@ -211,13 +142,13 @@ __global__ __launch_bounds__(RM_CT) void rm_connect_kernel(int E, const int* __r
                                                            double minR, double half_len, double half_wid, int nw,
                                                            const double* __restrict__ wtab,
                                                            double* __restrict__ w_out) {
-  __shared__ double psi_s[RM_PT][RM_PST], xs_s[RM_PT][RM_PST], ys_s[RM_PT][RM_PST];
-  __shared__ double psic_s[RM_PT][RM_NCHK];
-  __shared__ double wt[RM_WT * RM_WROW];
-  __shared__ double cmd_s[RM_PT][15], cur_s[RM_PT][3], init_s[RM_PT][3], d_s[RM_PT];
-  __shared__ int nseg_s[RM_PT], hit_s[RM_PT];
+  __shared__ double psi_s[RS_PT][RS_PST], xs_s[RS_PT][RS_PST], ys_s[RS_PT][RS_PST];
+  __shared__ double psic_s[RS_PT][RM_NCHK];
+  __shared__ double wt[WALL_TILE * WALL_ROW];
+  __shared__ double cmd_s[RS_PT][15], cur_s[RS_PT][3], init_s[RS_PT][3], d_s[RS_PT];
+  __shared__ int nseg_s[RS_PT], hit_s[RS_PT];
   const int tid = threadIdx.x;
-  const int e0 = blockIdx.x * RM_PT;
+  const int e0 = blockIdx.x * RS_PT;
   if (tid < 64) {
     const int p = tid >> 2, var = tid & 3, e = e0 + p;
     int ia = -1, ib = -1;
@@ -236,122 +167,73 @@ __global__ __launch_bounds__(RM_CT) void rm_connect_kernel(int E, const int* __r
     }
     double bc, tuv[3];
     int bi;
-    rm_best<true>(s, var, &bc, &bi, tuv);
+    rs_pair_best<false, true>(s, var, false, nullptr, nullptr, &bc, &bi, tuv);
     if (var == 0) {
       const double d = bc * minR;
       const bool ok = live && rm_finite(d);
       const int id = ok ? bi : 0;
       const int n = ok ? kRsN[id >> 2] : 0;
-      rm_cmd(id, n, tuv, cmd_s[p]);
+      rs_cmd_write_tuv(id, ok, tuv, cmd_s[p]);
       nseg_s[p] = n;
       hit_s[p] = 0;
       d_s[p] = ok ? d : __builtin_inf();
 #pragma unroll
       for (int c = 0; c < 3; c++) init_s[p][c] = cur_s[p][c] = a[c];
     }
-  } else if (nw <= RM_WT) {  // one tile holds the scene: loaded once
-    for (int i = tid - 64; i < nw * RM_WROW; i += RM_CT - 64) wt[i] = wtab[i];
+  } else if (nw <= WALL_TILE) {  // one tile holds the scene: loaded once
+    for (int i = tid - 64; i < nw * WALL_ROW; i += RM_CT - 64) wt[i] = wtab[i];
   }
   __syncthreads();
   int mx = 0;
-  for (int p = 0; p < RM_PT; p++) mx = nseg_s[p] > mx ? nseg_s[p] : mx;
+  for (int p = 0; p < RS_PT; p++) mx = nseg_s[p] > mx ? nseg_s[p] : mx;
   for (int s = 0; s <= mx; s++) {
     // ---- phase A: the serial chains, one lane each
-    if (tid < RM_PT) {
+    if (tid < RS_PT) {
       const int p = tid;
-      if (s < nseg_s[p] && !hit_s[p]) {
-        const double* cm = cmd_s[p] + 3 * s;
-        const double dt = __builtin_fabs(cm[0]) / 100;
-        const double c = (cm[2] * cm[1]) * dt;
-        double q = cur_s[p][2];
-        psi_s[p][0] = q;
-        for (int k = 0; k < 100; k++) {
-          q = q + c;
-          psi_s[p][k + 1] = q;
-        }
-        cur_s[p][2] = q;
-      }
-    } else if (tid >= 64 && tid < 64 + 2 * RM_PT) {
+      if (s < nseg_s[p] && !hit_s[p]) cur_s[p][2] = rs_heading_chain(cmd_s[p] + 3 * s, cur_s[p][2], psi_s[p]);
+    } else if (tid >= 64 && tid < 64 + 2 * RS_PT) {
       const int p = (tid - 64) >> 1, c = (tid - 64) & 1;
-      if (s >= 1 && s - 1 < nseg_s[p] && !hit_s[p]) {
-        double* inc = c == 0 ? xs_s[p] : ys_s[p];
-        double acc = cur_s[p][c];
-        // batches of 20 increments into registers first, so the LDS reads pipeline ahead of the chain
-        for (int u0 = 0; u0 < 100; u0 += 20) {
-          double v[20];
-#pragma unroll
-          for (int u = 0; u < 20; u++) v[u] = inc[u0 + u];
-#pragma unroll
-          for (int u = 0; u < 20; u++) {
-            acc = acc + v[u];
-            inc[u0 + u] = acc;
-          }
-        }
-        cur_s[p][c] = acc;
-      }
+      if (s >= 1 && s - 1 < nseg_s[p] && !hit_s[p])
+        cur_s[p][c] = rs_running_sum(c == 0 ? xs_s[p] : ys_s[p], cur_s[p][c]);
     }
     __syncthreads();
     // ---- phase C: block_collision_check of the columns that just landed
     if (nw > 0) {
       const int nitem = s == 0 ? 1 : RM_NCHK;
-      const int p = tid < RM_PT * nitem ? tid / nitem : 0, c = tid - p * nitem;
-      const bool active = tid < RM_PT * nitem && !hit_s[p] && (s == 0 ? nseg_s[p] > 0 : s - 1 < nseg_s[p]);
+      const int p = tid < RS_PT * nitem ? tid / nitem : 0, c = tid - p * nitem;
+      const bool active = tid < RS_PT * nitem && !hit_s[p] && (s == 0 ? nseg_s[p] > 0 : s - 1 < nseg_s[p]);
       double vq[8], vt[24];
       if (active) {  // the pose's rectangle (hybrid_astar_utils.jl:193) and its own SAT table, in registers
         const int k = 5 * c + 4;
         const double x = s == 0 ? init_s[p][0] : xs_s[p][k], y = s == 0 ? init_s[p][1] : ys_s[p][k];
         const double psi = s == 0 ? init_s[p][2] : psic_s[p][c];
-        double sp, cp, sy, cy;
-        mpj_sincos_bl(psi, &sp, &cp);
-        const double yaw = mpj_modpi_bl(psi);
-        mpj_sincos_bl(yaw, &sy, &cy);
-        rect_pts4(x + half_len * cp, y + half_len * sp, cy, sy, half_len, half_wid, vq);
-#pragma unroll
-        for (int e = 0; e < 4; e++) rect_edge(vq, e, vt + 6 * e);
+        vehicle_rect(x, y, psi, half_len, half_len, half_wid, vq, vt);
       }
       bool hit = false;
-      for (int w0 = 0; w0 < nw; w0 += RM_WT) {
-        const int tw = min(RM_WT, nw - w0);
-        if (nw > RM_WT) {  // block-uniform: the scene takes several tiles, each staged in turn
+      for (int w0 = 0; w0 < nw; w0 += WALL_TILE) {
+        const int tw = min(WALL_TILE, nw - w0);
+        if (nw > WALL_TILE) {  // block-uniform: the scene takes several tiles, each staged in turn
           __syncthreads();
-          for (int i = tid; i < tw * RM_WROW; i += RM_CT) wt[i] = wtab[(size_t)w0 * RM_WROW + i];
+          for (int i = tid; i < tw * WALL_ROW; i += RM_CT) wt[i] = wtab[(size_t)w0 * WALL_ROW + i];
           __syncthreads();
         }
-        if (active && !hit) {
-          for (int w = 0; w < tw; w++) {
-            const double* row = wt + w * RM_WROW;  // the same address in every lane: an LDS broadcast
-            bool fr = sat_table(row + 8, vq);      // ConvexCollision(wall, vehicle), utils.jl:64-74
-            if (fr) fr = sat_table(vt, row);
-            if (!fr) {
-              hit = true;
-              break;
-            }
-          }
-        }
+        if (active && !hit) hit = tile_first_hit(MP_SAT_BOTH, wt, tw, vq, vt) >= 0;
       }
       __syncthreads();  // every read of hit_s above comes before the writes below
       if (hit) hit_s[p] = 1;
       __syncthreads();
     }
     // ---- phase B: one thread per (path, step)
-    for (int i = tid; i < RM_PT * 100; i += RM_CT) {
+    for (int i = tid; i < RS_PT * 100; i += RM_CT) {
       const int p = i / 100, k = i - 100 * p;
       if (s < nseg_s[p] && !hit_s[p]) {
-        const double* cm = cmd_s[p] + 3 * s;
-        const double dt = __builtin_fabs(cm[0]) / 100, v = cm[1];
-        double sn, cs;
-        mpj_sincos_bl(psi_s[p][k], &sn, &cs);
-        double d0 = v * cs, d1 = v * sn;
-        d0 = d0 * minR;
-        d1 = d1 * minR;
-        xs_s[p][k] = d0 * dt;
-        ys_s[p][k] = d1 * dt;
+        rs_step_inc(cmd_s[p] + 3 * s, psi_s[p][k], minR, &xs_s[p][k], &ys_s[p][k]);
         if (k % 5 == 4) psic_s[p][k / 5] = psi_s[p][k + 1];
       }
     }
     __syncthreads();
   }
-  if (tid < RM_PT && e0 + tid < E) w_out[e0 + tid] = hit_s[tid] ? __builtin_inf() : d_s[tid];
+  if (tid < RS_PT && e0 + tid < E) w_out[e0 + tid] = hit_s[tid] ? __builtin_inf() : d_s[tid];
 }
 
 // -------------------------------------------------------------------- queries
@@ -446,12 +328,6 @@ __global__ __launch_bounds__(RM_DT) void rm_dijkstra_kernel(int n, int k, int B,
   }
 }
 
-bool all_finite(const double* v, size_t n) {
-  for (size_t i = 0; i < n; i++)
-    if (!std::isfinite(v[i])) return false;
-  return true;
-}
-
 // what both calls check of a scene
 int rm_check_scene(mp_ctx* ctx, const char* fn, int n, const double* nodes, int n_walls, const double* walls,
                    double minR, double len, double wid, int k) {
@@ -461,8 +337,8 @@ int rm_check_scene(mp_ctx* ctx, const char* fn, int n, const double* nodes, int 
   MP_CHECK(ctx, nodes && (walls || n_walls == 0), "%s: NULL argument", fn);
   MP_CHECK(ctx, std::isfinite(minR) && minR > 0, "%s: minR must be finite and positive", fn);
   MP_CHECK(ctx, std::isfinite(len) && std::isfinite(wid), "%s: non-finite vehicle size", fn);
-  MP_CHECK(ctx, all_finite(nodes, 3 * (size_t)n), "%s: non-finite node", fn);
-  MP_CHECK(ctx, n_walls == 0 || all_finite(walls, 5 * (size_t)n_walls), "%s: non-finite wall", fn);
+  MP_CHECK(ctx, mp_all_finite(nodes, 3 * (size_t)n), "%s: non-finite node", fn);
+  MP_CHECK(ctx, n_walls == 0 || mp_all_finite(walls, 5 * (size_t)n_walls), "%s: non-finite wall", fn);
   return MP_OK;
 }
 
@@ -472,7 +348,7 @@ int rm_walls(mp_ctx* ctx, int slot_in, int slot_tab, int n_walls, const double* 
   if (n_walls == 0) return MP_OK;
   int st = MP_OK;
   const double* dwalls = mp_upload(ctx, slot_in, walls, 5 * (size_t)n_walls, &st);
-  double* dtab = (double*)mp_ws(ctx, slot_tab, (size_t)n_walls * RM_WROW * sizeof(double));
+  double* dtab = (double*)mp_ws(ctx, slot_tab, (size_t)n_walls * WALL_ROW * sizeof(double));
   if (!dtab) return MP_ERR_NOMEM;
   if (st) return st;
   hipLaunchKernelGGL(rm_wall_kernel, dim3((unsigned)((n_walls + 63) / 64)), dim3(64), 0, ctx->stream, n_walls, dwalls,
@@ -508,7 +384,7 @@ int mp_roadmap_build(mp_ctx* ctx, int32_t n, const double* nodes, int32_t n_wall
                      (int*)dnbr, dpa, dpb);
   MP_HIP(ctx, hipGetLastError());
   mp_time_begin(ctx);
-  hipLaunchKernelGGL(rm_connect_kernel, dim3((unsigned)((E + RM_PT - 1) / RM_PT)), dim3(RM_CT), 0, ctx->stream, (int)E,
+  hipLaunchKernelGGL(rm_connect_kernel, dim3((unsigned)((E + RS_PT - 1) / RS_PT)), dim3(RM_CT), 0, ctx->stream, (int)E,
                      dpa, dpb, dP, minR, vehicle_len / 2, vehicle_wid / 2, (int)n_walls, dtab, dw);
   MP_HIP(ctx, hipGetLastError());
   mp_time_end(ctx);
@@ -530,8 +406,8 @@ int mp_roadmap_query(mp_ctx* ctx, int32_t n, const double* nodes, int32_t n_wall
            MP_ROADMAP_MAX_QUERIES);
   MP_CHECK(ctx, nbr && w && start && goal, "mp_roadmap_query: NULL input");
   MP_CHECK(ctx, found && cost && seq && seq_len && settled && direct_free, "mp_roadmap_query: NULL output");
-  MP_CHECK(ctx, all_finite(start, 3 * (size_t)B), "mp_roadmap_query: non-finite start");
-  MP_CHECK(ctx, all_finite(goal, 3 * (size_t)B), "mp_roadmap_query: non-finite goal");
+  MP_CHECK(ctx, mp_all_finite(start, 3 * (size_t)B), "mp_roadmap_query: non-finite start");
+  MP_CHECK(ctx, mp_all_finite(goal, 3 * (size_t)B), "mp_roadmap_query: non-finite goal");
   const size_t E = (size_t)n * k, nB = (size_t)B, Bk = nB * k, EQ = 2 * Bk + nB, V = (size_t)n + 2;
   for (size_t e = 0; e < E; e++)
     MP_CHECK(ctx, nbr[e] >= -1 && nbr[e] < n, "mp_roadmap_query: nbr[%zu] = %d outside [-1, %d]", e, nbr[e], n - 1);
@@ -578,7 +454,7 @@ int mp_roadmap_query(mp_ctx* ctx, int32_t n, const double* nodes, int32_t n_wall
   hipLaunchKernelGGL(rm_rank_kernel, dim3((unsigned)B), dim3(RM_RT), 0, ctx->stream, (int)n, (int)k, 1, (int)(n + B), 0,
                      dP, minR, dqn + Bk, dpa + Bk, dpb + Bk);
   MP_HIP(ctx, hipGetLastError());
-  hipLaunchKernelGGL(rm_connect_kernel, dim3((unsigned)((EQ + RM_PT - 1) / RM_PT)), dim3(RM_CT), 0, ctx->stream,
+  hipLaunchKernelGGL(rm_connect_kernel, dim3((unsigned)((EQ + RS_PT - 1) / RS_PT)), dim3(RM_CT), 0, ctx->stream,
                      (int)EQ, dpa, dpb, dP, minR, vehicle_len / 2, vehicle_wid / 2, (int)n_walls, dtab, dqw);
   MP_HIP(ctx, hipGetLastError());
   mp_time_begin(ctx);

@@ -287,12 +287,6 @@ struct RcCall {
   int32_t *path_idx, *path_n, *counters;
 };
 
-inline bool rc_finite(const double* v, size_t n) {
-  for (size_t i = 0; i < n; i++)
-    if (!std::isfinite(v[i])) return false;
-  return true;
-}
-
 inline int rc_validate(mp_ctx* ctx, const RcCall& C, int start_w) {
   if (!ctx) return MP_ERR_INVALID;
   const mp_rrt_params_t* p = C.p;
@@ -311,8 +305,8 @@ inline int rc_validate(mp_ctx* ctx, const RcCall& C, int start_w) {
       MP_CHECK(ctx, C.obs_count[s] >= 0 && C.obs_count[s] <= C.n_obs, "obs_count[%d] = %d: must be in 0 .. n_obs", s,
                C.obs_count[s]);
   const size_t nB = (size_t)C.B;
-  MP_CHECK(ctx, rc_finite(C.bound, 4 * nB) && rc_finite(C.start, start_w * nB) && rc_finite(C.goal, 2 * nB) &&
-                    std::isfinite(p->bias_rate) && std::isfinite(p->grow_min) && std::isfinite(p->grow_max) &&
+  MP_CHECK(ctx, mp_all_finite(C.bound, 4 * nB) && mp_all_finite(C.start, start_w * nB) &&
+                    mp_all_finite(C.goal, 2 * nB) && std::isfinite(p->bias_rate) && std::isfinite(p->grow_min) && std::isfinite(p->grow_max) &&
                     std::isfinite(p->goal_tolerance),
            "bounds, start, goal and settings must be finite");
   return MP_OK;

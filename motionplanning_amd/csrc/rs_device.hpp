@@ -1,8 +1,11 @@
-// rs_device.hpp — the Reeds–Shepp device code that hastar.hip (Hybrid A*'s RS_connected and rs_heuristic) and
-// reeds_shepp.hip (the batched Reeds–Shepp module) share: the twelve words as one straight-line program (rs_word),
-// the polar forms they start from (rs_pre), the four variants, Julia's findmin order and changeBasis
-// (PathPlanning/ReedsSheppsCurves/src/ReedsSheppsUtils.jl).  Include it after mp_jlmath.h (with MPJ_LANE_SAFE as the
-// including file needs it).  Everything has internal linkage, the __constant__ word tables included.
+// rs_device.hpp — the Reeds–Shepp device code that hastar.hip (Hybrid A*'s RS_connected and rs_heuristic),
+// reeds_shepp.hip (the batched Reeds–Shepp module) and roadmap.hip (the roadmap's edges) share: the twelve words as
+// one straight-line program (rs_word), the polar forms they start from (rs_pre), the four variants, Julia's findmin
+// order and changeBasis (PathPlanning/ReedsSheppsCurves/src/ReedsSheppsUtils.jl); on top of them a candidate's
+// command table (rs_cmd_write, rs_cmd_write_tuv), allpath + findmin of a pair in four lanes (rs_pair_best) and
+// createPath's three chains (rs_heading_chain, rs_running_sum, rs_step_inc).  Include it after mp_jlmath.h (with
+// MPJ_LANE_SAFE as the including file needs it).  Everything has internal linkage, the __constant__ word tables
+// included.
 #pragma once
 #include "../../include/mp_jlmath.h"
 
@@ -133,7 +136,7 @@ __device__ __forceinline__ double rs_word(int w_, const RsPre& R, Cmd* c, double
   else if (w <= 6) valid = rho <= 4;
   else if (w == 7) valid = (rho <= 6) && (0 <= u1) && (u1 <= 1);
   else valid = rho >= 4;
-  if (tuv) {  // the word's segment lengths: with (w, variant) they determine its commands (cmd_from_tuv)
+  if (tuv) {  // the word's segment lengths: with (w, variant) they determine its commands (rs_cmd_write_tuv)
     tuv[0] = t;
     tuv[1] = u;
     tuv[2] = v;
@@ -163,16 +166,152 @@ __device__ __forceinline__ bool rs_before(double a, int ia, double b, int ib) {
   return (a < b) || (a == b && ia < ib);
 }
 
-// allpath + findmin (ReedsSheppsUtils.jl:383-436, hybrid_astar_utils.jl rs_heuristic /
-// RS_connected).  The word loop is wave-uniform (no divergent 12-way switch): lane&3 is
-// the variant (plain, timeflip, reflect, reverse) of candidate id = 4(w-1)+variant.
-// Returns the winning cost in every lane; *best_id = winning id; if cm != nullptr the
-// winner's commands [5][3] (distance, gear, steer) are written to cm (LDS) by one lane.
+// The variant (plain, timeflip, reflect, reverse) of normalised state s that allpath hands to the words.
 __device__ __forceinline__ void rs_variant(const double* s, int var, double* q) {
   q[0] = s[0]; q[1] = s[1]; q[2] = s[2];
   if (var == 1) { q[0] = -q[0]; q[2] = -q[2]; }       // timeflip
   else if (var == 2) { q[1] = -q[1]; q[2] = -q[2]; }  // reflect
   else if (var == 3) { q[0] = -q[0]; q[1] = -q[1]; }  // reverse
+}
+
+// ------------------------------------------------------------ command tables
+// A candidate's command table o[5][3] (distance, gear, steer) with allpath's variant signs (timeflip: gear,
+// reflect: steer, reverse: both) from the rows of the plain word that rs_word left in c; rows >= c.n are 0, and all
+// rows where !ok (the candidate's cost is Inf).  Every lane forms the rows, the lanes with `store` write them.
+__device__ __forceinline__ void rs_cmd_write(const Cmd& c, bool ok, int var, bool store, double* o) {
+  const int n = ok ? c.n : 0;
+#pragma unroll
+  for (int r = 0; r < 5; r++) {
+    double tr = 0.0, ge = 0.0, st = 0.0;
+    if (r < n) {
+      tr = c.tr[r];
+      ge = c.ge[r];
+      st = c.st[r];
+      if (var == 1 || var == 3) ge = -1 * ge;
+      if (var == 2 || var == 3) st = -1 * st;
+    }
+    if (store) {
+      o[3 * r] = tr;
+      o[3 * r + 1] = ge;
+      o[3 * r + 2] = st;
+    }
+  }
+}
+// The same table from candidate id = 4(w-1) + variant and the word's (t, u, v), without evaluating the word again:
+// the rows it needs come from the word tables (none where !ok), the signs and stores are rs_cmd_write's.
+__device__ __forceinline__ void rs_cmd_write_tuv(int id, bool ok, const double* tuv, double* o) {
+  const int wi = id >> 2;
+  Cmd c;
+  c.n = ok ? kRsN[wi] : 0;
+#pragma unroll
+  for (int r = 0; r < 5; r++)
+    if (r < c.n) {
+      const int code = kRsTr[wi][r];
+      c.tr[r] = code == 0 ? tuv[0] : code == 1 ? tuv[1] : code == 2 ? tuv[2] : PI2;
+      c.ge[r] = kRsGe[wi][r];
+      c.st[r] = kRsSt[wi][r];
+    }
+  rs_cmd_write(c, ok, id & 3, true, o);
+}
+
+// ------------------------------------------------------------ allpath + findmin
+// allpath + findmin (ReedsSheppsUtils.jl:383-436, hybrid_astar_utils.jl rs_heuristic / RS_connected) of one pose
+// pair, normalised state s, in the four lanes 4j..4j+3 of a wave: lane & 3 = var is the variant of candidate
+// id = 4(w-1) + var, and the word loop is wave-uniform (no divergent 12-way switch).  The winner's cost and id come
+// back in all four lanes (rs_before is a total order, so per lane then across lanes finds allpath's winner) and,
+// when TUV, so do its word's (t, u, v).  Where `live`, every candidate's cost goes to cost[48] (may be null) and,
+// when WC, its command table to cmds[48][5][3].
+template <bool WC, bool TUV>
+__device__ __forceinline__ void rs_pair_best(const double* s, int var, bool live, double* __restrict__ cost,
+                                             double* __restrict__ cmds, double* bc_out, int* bi_out,
+                                             double* tuv_out) {
+  double q[3];
+  rs_variant(s, var, q);
+  const RsPre R = rs_pre(q);
+  double bc = __builtin_inf();
+  int bi = 1 << 20;
+  double bt[3] = {0.0, 0.0, 0.0};
+#pragma unroll 1
+  for (int w = 1; w <= 12; w++) {
+    Cmd c;
+    double tv[3];
+    const double cst = rs_word(w, R, WC ? &c : nullptr, TUV ? tv : nullptr);
+    const int id = 4 * (w - 1) + var;
+    if (rs_before(cst, id, bc, bi)) {
+      bc = cst;
+      bi = id;
+      if (TUV) { bt[0] = tv[0]; bt[1] = tv[1]; bt[2] = tv[2]; }
+    }
+    if (live && cost) cost[id] = cst;
+    if (WC && live) rs_cmd_write(c, cst < __builtin_inf(), var, true, cmds + id * 15);
+  }
+#pragma unroll
+  for (int o = 2; o >= 1; o >>= 1) {
+    const double ov = __shfl_xor(bc, o);
+    const int oi = __shfl_xor(bi, o);
+    double ot[3] = {0.0, 0.0, 0.0};
+    if (TUV) {
+      ot[0] = __shfl_xor(bt[0], o);
+      ot[1] = __shfl_xor(bt[1], o);
+      ot[2] = __shfl_xor(bt[2], o);
+    }
+    if (rs_before(ov, oi, bc, bi)) {
+      bc = ov;
+      bi = oi;
+      if (TUV) { bt[0] = ot[0]; bt[1] = ot[1]; bt[2] = ot[2]; }
+    }
+  }
+  *bc_out = bc;
+  *bi_out = bi;
+  if (TUV) { tuv_out[0] = bt[0]; tuv_out[1] = bt[1]; tuv_out[2] = bt[2]; }
+}
+
+// ------------------------------------------------------------ createPath
+// createPath / createActPath (ReedsSheppsUtils.jl:411-466; operand order of the oracle's or_ha_act_path), a block
+// of RS_PT command tables segment by segment over LDS rows of RS_PST doubles.  Three serial chains, each kept in
+// order for the bits of the reference; cm = the segment's command row (distance, gear, steer).  The closed form of
+// repeated addition (mpj_rep_add_ok) is not used here: see DESIGN.md.
+constexpr int RS_PT = 16;    // paths per block
+constexpr int RS_PST = 101;  // LDS row stride in doubles (100 steps + 1: ψ_0..ψ_100; odd against bank conflicts)
+
+// The heading recurrence ψ_{k+1} = ψ_k + (steer*gear)*Δt from ψ_0 = q into psi[0..100]; returns ψ_100.
+__device__ __forceinline__ double rs_heading_chain(const double* cm, double q, double* psi) {
+  const double dt = __builtin_fabs(cm[0]) / 100;
+  const double c = (cm[2] * cm[1]) * dt;
+  psi[0] = q;
+  for (int k = 0; k < 100; k++) {
+    q = q + c;
+    psi[k + 1] = q;
+  }
+  return q;
+}
+
+// The running sum of a segment's 100 increments from acc, in place over them; returns the last.  Batches of 20
+// increments into registers first, so the LDS reads pipeline ahead of the chain.
+__device__ __forceinline__ double rs_running_sum(double* inc, double acc) {
+  for (int u0 = 0; u0 < 100; u0 += 20) {
+    double v[20];
+#pragma unroll
+    for (int u = 0; u < 20; u++) v[u] = inc[u0 + u];
+#pragma unroll
+    for (int u = 0; u < 20; u++) {
+      acc = acc + v[u];
+      inc[u0 + u] = acc;
+    }
+  }
+  return acc;
+}
+
+// One step's increments ((gear*cos ψ)*minR)*Δt, ((gear*sin ψ)*minR)*Δt.
+__device__ __forceinline__ void rs_step_inc(const double* cm, double psi, double minR, double* dx, double* dy) {
+  const double dt = __builtin_fabs(cm[0]) / 100, v = cm[1];
+  double sn, cs;
+  mpj_sincos_bl(psi, &sn, &cs);
+  double d0 = v * cs, d1 = v * sn;
+  d0 = d0 * minR;
+  d1 = d1 * minR;
+  *dx = d0 * dt;
+  *dy = d1 * dt;
 }
 
 // changeBasis with sin/cos of init's heading given (the lattice-heading tables)

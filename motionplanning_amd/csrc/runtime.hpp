@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -175,6 +176,13 @@ int mp_as_table_status(mp_ctx* ctx);
   do {                                                        \
     if (!(cond)) return mp_fail((ctx), MP_ERR_INVALID, __VA_ARGS__); \
   } while (0)
+
+// Whether v[0..n) are all finite: what the calls check of their floating-point inputs.
+static inline bool mp_all_finite(const double* v, size_t n) {
+  for (size_t i = 0; i < n; i++)
+    if (!std::isfinite(v[i])) return false;
+  return true;
+}
 
 // Copy host -> device scratch slot (nullptr-safe); returns device pointer or nullptr.
 template <typename T>

@@ -23,7 +23,7 @@ __all__ = ["rs_allpath", "create_path", "cost_matrix", "changeBasis", "allpath",
 
 N_CANDIDATES = 48
 MAX_PATH = 501   # 100 steps x 5 segments + the start
-PATH_TILE = 16   # command tables per workgroup of mp_rs_create_path (RS_PT, csrc/reeds_shepp.hip)
+PATH_TILE = 16   # command tables per workgroup of mp_rs_create_path (RS_PT, csrc/rs_device.hpp)
 
 
 # ------------------------------------------------------------------ batched calls, C layout
