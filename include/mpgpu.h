@@ -572,6 +572,48 @@ int mp_grid_inflate(mp_ctx* ctx, int32_t flags, int32_t B, int32_t nx, int32_t n
 int mp_grid_path_clearance(mp_ctx* ctx, int32_t flags, int32_t B, int32_t nx, int32_t ny, const uint8_t* mask,
                            const int32_t* path, const int32_t* path_n, int32_t stride, int32_t* min_d2, int32_t* at);
 
+/* ------------------------------------------------- goal-distance fields */
+#define MP_FIELD_TO_SOURCE 1                /* flags bit 0: the cost of travelling from each cell to the source */
+#define MP_FIELD_MOVES_REF 0x7F             /* dka_utils.jl:177's seven distinct moves (no (-1, +1)) */
+#define MP_FIELD_MOVES_8 0xFF
+#define MP_FIELD_MOVES_4 0x69
+#define MP_FIELD_MAX_BATCH_CELLS (1 << 26)  /* B*nx*ny of one call: 512 MiB of field */
+
+/* The cost from one source cell to every cell of each of B occupancy maps, and paths read off it (an extension:
+ * planDKA! run until its open list is empty leaves these labels in nodes_collection, dka_utils.jl:73).
+ *
+ * Geometry (bound[B][4], nx, ny, factors, real -> cell) is mp_grid_plan's, mask[B][ny][nx] that of
+ * MP_GRID_OBS_MASK.  moves is a set over the neighbours (dx, dy), bit 0 .. bit 7:
+ *   (-1,0) (-1,-1) (1,-1) (1,0) (1,1) (0,-1) (0,1) (-1,1)
+ * and move d costs c(d) = sqrt(double(dx^2)*(xf*xf) + double(dy^2)*(yf*yf)) (dka_utils.jl:189).  A cell is a member
+ * iff it is on the grid and its mask byte is nonzero, or it is the source (the reference never tests its start).
+ * field[source] = 0; every other member holds the unique solution of f[v] = min over moves u -> v of
+ * fl(f[u] + c(u -> v)) in IEEE double -- bit for bit planDKA!'s final_cost to v with MP_FIELD_MOVES_REF --;
+ * non-members and unreached members hold +Inf.  n_reached[b] counts the finite cells.  A source off the grid gives
+ * an all-+Inf field and n_reached = 0 (mp_dka_plan keeps a start one cell outside; this call does not).
+ * With MP_FIELD_TO_SOURCE the graph is reversed: f[v] = min over d of fl(f[v + d] + c(d)), the cost of travelling
+ * from v to the source; the sum accumulates from the source, so it is not claimed equal to planDKA! from v.
+ *
+ * Queries: query q reads map q_map[q] at the cell of q_real[q].  q_cost[q] is the field there; +Inf and
+ * path_n = 0 when the cell is off the grid or unreached.  The path is in travel order, as Encode indices (it feeds
+ * mp_grid_path_clearance unchanged): source -> query, built backwards by taking from v the lowest-bit move d with
+ * u = v - d finite and fl(f[u] + c(d)) == f[v]; with MP_FIELD_TO_SOURCE query -> source, u = v + d.  path_n[q] is
+ * the full length; only the first min(path_n, stride) entries of path[q][stride] are written.  path_length[q] is
+ * the planners' left fold over the TransferCoordinate rows of the whole path.
+ *
+ *   flags: MP_FIELD_TO_SOURCE.  moves: 1 .. 0xFF.  B >= 1, nx, ny >= 2, nx*ny <= MP_GRID_MAX_CELLS,
+ *   B*nx*ny <= MP_FIELD_MAX_BATCH_CELLS; finite bounds and positive factors; Q >= 0, q_map in 0 .. B-1.
+ *   field and n_reached may each be NULL; Q = 0 takes every query pointer NULL; Q > 0 needs q_map, q_real and
+ *   q_cost; path, path_n and path_length come all together (stride >= 1) or not at all.  At least one output must
+ *   be asked for.  A violation: MP_ERR_INVALID, nothing launched or written.  A workspace that cannot be had:
+ *   MP_ERR_NOMEM, nothing launched or written.  Workspaces: 9 bytes per cell of the batch; with paths also
+ *   4 bytes per query and member cell of its map.  More than nx*ny + 1 relaxation rounds: MP_ERR_NUMERIC (it
+ *   cannot happen: a round settles at least the cells one more move away). */
+int mp_grid_field(mp_ctx* ctx, int32_t flags, int32_t moves, int32_t B, int32_t nx, int32_t ny, const double* bound,
+                  const double* source_real, const uint8_t* mask, double* field, int32_t* n_reached, int32_t Q,
+                  const int32_t* q_map, const double* q_real, int32_t stride, double* q_cost, int32_t* path,
+                  int32_t* path_n, double* path_length);
+
 /* ----------------------------------------------------------- RRT / RRT* */
 #define MP_RRT_MAX_ITER 1000000 /* cap on n_iter (the tree workspace is 48 bytes per node and scene; 64 for mp_rrtnh_plan) */
 

@@ -30,7 +30,7 @@ using Interpolations: interpolate, Gridded, Constant, Previous, linear_interpola
 
 export MPPIPlan, MPPIClosedLoop, planHybridAstar!, mppi_plan_batch, mppi_plan_sharded, comm_init, mppi_closed_loop_batch,
        rollout_batch, ha_expand, ha_rs_connect, ha_astar_table, astar_plan_batch, dka_plan_batch, bfs_plan_batch, grid_plan_batch, rrt_plan_batch, rrtnh_plan_batch,
-       grid_rasterize, grid_distance, grid_inflate, grid_path_clearance, ha_allpath, ha_neighbor_origin, retrieve_batch!, track_batch!, ilqr_rollout, ilqr_backward!, ilqr_forward!,
+       grid_rasterize, grid_distance, grid_inflate, grid_path_clearance, grid_field, ha_allpath, ha_neighbor_origin, retrieve_batch!, track_batch!, ilqr_rollout, ilqr_backward!, ilqr_forward!,
        ilqr_solve!, vehicle_euler!, ctx_join, rs_allpath, rs_create_path, rs_cost_matrix, changeBasis, allpath,
        createPath, createActPath
 
@@ -660,6 +660,33 @@ function grid_path_clearance(mask::Array{UInt8,3}, path::Matrix{Int32}, path_n::
         (Ptr{Cvoid}, Int32, Int32, Int32, Int32, Ptr{UInt8}, Ptr{Int32}, Ptr{Int32}, Int32, Ptr{Int32}, Ptr{Int32}),
         c, border ? MP_MAP_BORDER : Int32(0), B, nx, ny, mask, path, path_n, size(path, 1), min_d2, at), c)
     return (; min_d2, at)
+end
+
+"""
+    grid_field(mask, bound, source_real; moves = 0x7f, to_source = false, q_map = Int32[], q_real = zeros(2, 0), stride = 0)
+
+Float64 (nx, ny, B): the cost of the cheapest way from the cell of source_real (2, B) to every cell of the free-cell
+masks (nx, ny, B) over the moves in the bit set moves (0x7f: planDKA!'s seven, 0xff: eight, 0x69: four), Inf on
+blocked and unreached cells, and n_reached (B) (mp_grid_field); to_source gives the cost from each cell to the source.
+With queries (q_map 0-based maps, q_real (2, Q), stride > 0) also q_cost, path (stride, Q) of Encode indices in travel
+order, path_n (the full length; the path is cut at stride) and path_length.
+"""
+function grid_field(mask::Array{UInt8,3}, bound::Matrix{Float64}, source_real::Matrix{Float64}; moves = 0x7f,
+                    to_source = false, q_map::Vector{Int32} = Int32[], q_real::Matrix{Float64} = zeros(2, 0), stride = 0)
+    nx, ny, B = size(mask); Q = length(q_map)
+    size(bound, 2) == B && size(source_real, 2) == B && size(q_real, 2) == Q || error("grid_field: one bound and source per map, one point per query")
+    field = zeros(Float64, nx, ny, B); n_reached = zeros(Int32, B)
+    paths = Q > 0 && stride > 0
+    q_cost = zeros(Float64, Q); path_length = zeros(Float64, Q)
+    path = fill(Int32(-1), max(stride, 1), Q); path_n = zeros(Int32, Q)
+    c = ctx()
+    check(GC.@preserve mask bound source_real field n_reached q_map q_real q_cost path path_n path_length ccall((:mp_grid_field, libmpgpu), Cint,
+        (Ptr{Cvoid}, Int32, Int32, Int32, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}, Ptr{Float64}, Ptr{Int32},
+         Int32, Ptr{Int32}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}),
+        c, to_source ? Int32(1) : Int32(0), Int32(moves), B, nx, ny, bound, source_real, mask, field, n_reached, Q,
+        Q > 0 ? pointer(q_map) : C_NULL, Q > 0 ? pointer(q_real) : C_NULL, stride, Q > 0 ? pointer(q_cost) : C_NULL,
+        paths ? pointer(path) : C_NULL, paths ? pointer(path_n) : C_NULL, paths ? pointer(path_length) : C_NULL), c)
+    return (; field, n_reached, q_cost, path, path_n, path_length)
 end
 
 struct RrtParams    # mp_rrt_params (PathPlanning/RRT/src/types.jl:19-39)

@@ -178,6 +178,13 @@ MP_MAP_D2_NONE = 2147483647
 MP_MAP_MAX_BATCH_CELLS = 1 << 28
 MP_MAP_MAX_SIDE = 32768
 
+MP_GRID_MAX_CELLS = 1 << 22
+MP_FIELD_TO_SOURCE = 1
+MP_FIELD_MOVES_REF = 0x7F
+MP_FIELD_MOVES_8 = 0xFF
+MP_FIELD_MOVES_4 = 0x69
+MP_FIELD_MAX_BATCH_CELLS = 1 << 26
+
 MP_TRACK_DONE = 0
 MP_TRACK_MAXSTEP = 1
 MP_TRACK_NOPATH = 2
@@ -230,6 +237,7 @@ SIGNATURES = {
     "mp_grid_distance": (ctypes.c_int, [_V, _I, _I, _I, _I, _V, _V]),
     "mp_grid_inflate": (ctypes.c_int, [_V, _I, _I, _I, _I, _V, _V, _V]),
     "mp_grid_path_clearance": (ctypes.c_int, [_V, _I, _I, _I, _I, _V, _V, _V, _I, _V, _V]),
+    "mp_grid_field": (ctypes.c_int, [_V, _I, _I, _I, _I, _I, _V, _V, _V, _V, _V, _I, _V, _V, _I, _V, _V, _V, _V]),
     "mp_rrt_plan": (ctypes.c_int, [_V, ctypes.POINTER(RRTParams), _I, _V, _V, _V, _I] + [_V] * 13),
     "mp_rrtnh_plan": (ctypes.c_int, [_V, ctypes.POINTER(RRTParams), _I, _V, _V, _V, _I] + [_V] * 13),
     "mp_ha_retrieve_path": (ctypes.c_int, [_V, _I, _V, _V, _V, _I] + [_V] * 8),

@@ -381,7 +381,10 @@ __global__ __launch_bounds__(64) void bfs_search_kernel(AsArgs A) {
 }
 
 // ---------------------------------------------------------------- host
-// defineAstar (setup.jl:15-18): factors and Int(floor(...)) cells; false when a cell is not an int
+}  // namespace
+
+// defineAstar (setup.jl:15-18): factors and Int(floor(...)) cells; false when a cell is not an int (declared in
+// gridsearch.hpp: gridfield.hip converts with the same code)
 bool as_factors(const double* b, int nx, int ny, double* ge) {
   ge[0] = b[0];
   ge[1] = b[2];
@@ -396,6 +399,8 @@ bool as_cell(const double* ge, const double* real, int* cell) {
   cell[1] = (int)cy;
   return true;
 }
+
+namespace {
 
 // masks + searches on the context stream (no synchronisation).  obs_dev: [scenes][n_obs][kind] on the device;
 // kind MP_GRID_OBS_MASK: the masks are in WS_AS_MASK already.  node_ws: the node workspace of gridbig.hip's

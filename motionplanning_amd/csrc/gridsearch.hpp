@@ -49,3 +49,7 @@ __device__ __forceinline__ double as_path_length(const T* rev, int cnt, int nx, 
 // nx*ny = N cells, and their launch on the context stream (A complete: mask, err and cap set)
 size_t gb_node_bytes(int planner, size_t searches, int N);
 int gb_launch(mp_ctx* ctx, int planner, int searches, void* node_ws, const AsArgs& A);
+
+// astar.hip: defineAstar's factors (ge = [xmin, ymin, x_factor, y_factor]) and real -> cell conversion on the host
+bool as_factors(const double* b, int nx, int ny, double* ge);
+bool as_cell(const double* ge, const double* real, int* cell);

@@ -139,6 +139,13 @@ enum {
   WS_MAP_PATH,    // ... mp_grid_path_clearance's paths
   WS_MAP_PN,      // ... their lengths
   WS_MAP_RES,     // ... min_d2[B] and at[B]
+  WS_FIELD_F,     // goal-distance fields (gridfield.hip): the fields, 8 bytes per cell
+  WS_FIELD_MASK,  // ... the caller's masks
+  WS_FIELD_MAP,   // ... per map: move costs, geometry, source cell
+  WS_FIELD_TILE,  // ... per tile: two rounds of dirty bytes, the finite-cell counts; the change stamp
+  WS_FIELD_Q,     // ... the queries and their results
+  WS_FIELD_PATH,  // ... the paths as the caller gets them
+  WS_FIELD_WALK,  // ... the walks' cells in walk order
   WS_COUNT
 };
 
